@@ -10,6 +10,10 @@ A "step" is one full training iteration of gans/trainer.py: G step, D step, lazy
 all-reduce over RCCL when N > 1.  Inputs are synthetic and resident in HBM (z ~ N(0,1), real
 range images from the synthetic depth generator).  Weak scaling: per-GPU batch fixed at 64.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps iterations, writes the last one's outputs when --dump-outputs DIR is
+given, and prints the line.  --full adds every other measurement: separately timed plain / R1 / ADA p = 0 iterations,
+the bf16-epilogue step, the per-kernel roofline probes and the CPU baseline.
 """
 import argparse
 import json
@@ -42,6 +46,14 @@ def parse():
                          "operands of the discriminator's ResidualBlocks as OCP e4m3 on v_mfma_f32_16x16x32_fp8_fp8 "
                          "(BASELINE configs[4], quoted at --res 128x1024 --batch-per-gpu 32; DESIGN.md)")
     ap.add_argument("--ada-p", type=float, default=0.6)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the separately timed plain / R1 / ADA p = 0 "
+                         "iterations, the bf16-epilogue step, the roofline probes and the CPU baseline (--no-extra and "
+                         "--no-cpu-baseline drop parts of it).  Off: set up, warm up, time --steps steps, dump, print")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64): its returned scalars and the models' state (a fixed seeded sample of each, see "
+                         "dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly instead of replaying hipGraphs")
     ap.add_argument("--cpu-batch", type=int, default=4)
@@ -54,14 +66,17 @@ def parse():
                     help="precision of the discriminator's epilogue (mbstd, 3x3 513->512 conv, Linear 65536->512): fp32 "
                          "is what the reference runs (dusty_v2.py:394-395) and what `value` is quoted on; bf16 is an "
                          "opt-in whose throughput is reported next to it as `extra.value_d_epilogue_bf16`")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurement points (ADA p = 0, bf16 "
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra measurement points (ADA p = 0, bf16 "
                     "epilogue, separately timed R1 / plain iterations)")
     ap.add_argument("--stamp", default=os.environ.get("DGV2_BENCH_STAMP"),
                     help="write {src_sha16, lib_sha16, argv} of THIS process to the given file before anything is "
                          "timed: a profiler-wrapped run leaves the identity of the kernels it traced next to its "
                          "trace, and scripts/step_listing.py copies that stamp instead of hashing whatever tree it is "
                          "later run in (scripts/refresh_profiles.sh)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_cfg(args, rank, world):
@@ -467,14 +482,58 @@ def build_trainer(args, rank, world, d_epilogue=None):
     return cfg, trainer
 
 
-def timed_steps(trainer, first_it, n, barrier):
-    """Wall time of `n` consecutive iterations first_it, first_it+1, ... bracketed by barrier + synchronize."""
+def timed_steps(trainer, first_it, n, barrier, last=None):
+    """Wall time of `n` consecutive iterations first_it, first_it+1, ... bracketed by barrier + synchronize.  `last`, a
+    dict, receives what the last of them returned."""
     barrier()
     t0 = time.perf_counter()
     for k in range(n):
-        trainer.step(first_it + k)
+        out = trainer.step(first_it + k)
     barrier()
-    return time.perf_counter() - t0
+    dt = time.perf_counter() - t0
+    if last is not None:
+        last.update(out)
+    return dt
+
+
+DUMP_SAMPLE = 1 << 20   # elements of one dumped array at most (4 MB in float32); larger ones are sampled
+
+
+def _dump_name(key):
+    return "".join(c if c.isalnum() or c in "._-" else "_" for c in key)
+
+
+def dump_outputs(path, arrays):
+    """Writes name -> tensor / number as path/<name>.npy: numbers and one-element tensors as float64 of shape (1,),
+    every other tensor flattened as float32 -- whole up to DUMP_SAMPLE elements, else the DUMP_SAMPLE elements at the
+    positions (sorted) drawn by numpy's default_rng(0) from its numel(), the same for every run with the same shapes."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        if not torch.is_tensor(v) or v.numel() == 1:
+            a = np.asarray([float(v)], dtype=np.float64)
+        else:
+            flat = v.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.float().cpu().numpy()
+        np.save(os.path.join(path, _dump_name(name) + ".npy"), a)
+
+
+def model_state(module):
+    """Every floating-point entry of a module's state dict (parameters and buffers), flattened in key order."""
+    return torch.cat([v.detach().reshape(-1).float() for v in module.state_dict().values() if v.is_floating_point()])
+
+
+def step_outputs(trainer, out):
+    """What one training iteration hands its caller: the scalars Trainer.step returns and the state it leaves in G, D
+    and G_ema (weights after both Adam steps and the EMA update, the mapping network's running statistics)."""
+    arrays = {"step." + k: v for k, v in sorted(out.items())}
+    arrays["ada_p"] = trainer.A.p
+    for name in ("G", "D", "G_ema"):
+        arrays[name + ".state"] = model_state(getattr(trainer, name))
+    return arrays
 
 
 def warm(trainer, cfg, n):
@@ -570,20 +629,25 @@ def main():
             barrier()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                run()
+                res = run()
             barrier()
         dt, every = max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            last = out if graph is not None else res   # the captured graph's outputs hold its last replay's
+            dump_outputs(args.dump_outputs, {k: v for k, v in last.items() if torch.is_tensor(v)})
         if rank == 0:
-            _emit(json.dumps({
+            line = {
                 "metric": f"range-images/sec (generator forward) on dusty_v2 {args.res}",
                 "value": args.steps * args.batch_per_gpu * world / dt, "unit": "range-images/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                 "config": {"workload": f"configs[1]: dusty_v2 generator-only forward (eval, EMA weights), {args.res}",
                            "global_batch": args.batch_per_gpu * world, "per_gpu_batch": args.batch_per_gpu,
-                           "parallelism": f"dp{world}", "hip_graph": graph is not None},
-                "roofline": gfwd_probe_roofline(args, dt / args.steps) if args.res == "64x512" else None,
-                "roofline_modconv": modconv_probe(args)}), out_fd)
+                           "parallelism": f"dp{world}", "hip_graph": graph is not None}}
+            if args.full:
+                line.update(roofline=gfwd_probe_roofline(args, dt / args.steps) if args.res == "64x512" else None,
+                            roofline_modconv=modconv_probe(args))
+            _emit(json.dumps(line), out_fd)
         if dist_on:
             dist.barrier()   # leave together: rank 0 may still be printing
             dist.destroy_process_group()
@@ -592,12 +656,15 @@ def main():
     warm(trainer, cfg, args.warmup)
     # Lazy R1 runs on every 16th iteration.  The K timed iterations start where they contain ceil(K / 16) of them (K = 20:
     # two, i.e. 1/10 instead of 1/16), so the timed region never under-counts the regulariser whatever --steps is;
-    # `extra` reports the separately timed plain / R1 iterations and the exactly 1/16-weighted step next to it.
+    # with --full, `extra` reports the separately timed plain / R1 iterations and the exactly 1/16-weighted step next to it.
     lazy = int(cfg.training.lazy.gp)
     n_r1 = -(-args.steps // lazy)
     first_it = lazy * n_r1 - args.steps + 1 if args.steps % lazy else 1
     first_it = max(first_it, 1)
-    dt, every = max_over_ranks(timed_steps(trainer, first_it, args.steps, barrier))
+    last = {}
+    dt, every = max_over_ranks(timed_steps(trainer, first_it, args.steps, barrier, last))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(trainer, last))
     r1_in_region = sum(1 for k in range(args.steps) if (first_it + k) % lazy == 0)
     imgs = args.steps * args.batch_per_gpu * world
     value = imgs / dt
@@ -606,7 +673,7 @@ def main():
              "per_rank_images_per_s": [args.steps * args.batch_per_gpu / t for t in every],
              "world_size_seen": dist.get_world_size() if dist_on else 1,
              "backend": dist.get_backend() if dist_on else None}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # plain and R1 iterations timed on their own (every rank takes part: the steps contain collectives)
         t_plain = max_over_ranks(timed_steps(trainer, 1, 6, barrier))[0] / 6
         t_r1 = sum(max_over_ranks(timed_steps(trainer, lazy, 1, barrier))[0] for _ in range(3)) / 3
@@ -635,11 +702,12 @@ def main():
     extra["status_word"] = dgv2_native.status_read()   # 0: no kernel met a broken promise (x_exact) during the run
     if extra["status_word"]:
         raise AssertionError(f"a kernel reported a broken promise: status word {extra['status_word']} (include/dgv2.h)")
-    roof = x3_probe(args) if rank == 0 else None
-    roof_s2 = s2dgrad_probe(args) if rank == 0 else None
-    roof_strip = roofline_probe(args) if rank == 0 else None
-    roof_mod = modconv_levels(args) if rank == 0 else None
-    if not args.no_extra and world == 1 and args.dtype == "bf16" and args.res == "64x512":
+    probe = args.full and rank == 0
+    roof = x3_probe(args) if probe else None
+    roof_s2 = s2dgrad_probe(args) if probe else None
+    roof_strip = roofline_probe(args) if probe else None
+    roof_mod = modconv_levels(args) if probe else None
+    if args.full and not args.no_extra and world == 1 and args.dtype == "bf16" and args.res == "64x512":
         # the same step with the discriminator epilogue in bf16 (opt-in; NOT what `value` is quoted on)
         other = "bf16" if args.d_epilogue == "fp32" else "fp32"
         del trainer
@@ -671,20 +739,19 @@ def main():
                        "pe_table_precomputed": os.environ.get("DGV2_NO_CONST_CACHE") is None},
             "model_tflops_per_gpu": value / world * GFLOP_PER_IMG_ITER / 1e3 if args.res == "64x512" else None,
             "extra": extra,
-            "roofline_conv_x3": roof,
-            "roofline_conv_s2dgrad": roof_s2,
-            "roofline_strip": roof_strip,
-            "roofline_modconv": roof_mod,
         }
-        # `roofline` = the probe of the instance the committed statistics rank highest
-        key, name, pct = dominant_instance()
-        chosen = {"conv_x3": roof, "s2dgrad": roof_s2, "strip": roof_strip}.get(key) or roof
-        out["roofline"] = None if chosen is None else dict(
-            chosen, selected_by=f"largest share of the training iteration among the probed (kernel, grid) instances in {STATS_FILE}: "
-                                 f"{pct} % ({key})",
-            stats_measured_on_this_tree=stats_current())
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_batch)
+        if args.full:
+            out.update(roofline_conv_x3=roof, roofline_conv_s2dgrad=roof_s2, roofline_strip=roof_strip,
+                       roofline_modconv=roof_mod)
+            # `roofline` = the probe of the instance the committed statistics rank highest
+            key, name, pct = dominant_instance()
+            chosen = {"conv_x3": roof, "s2dgrad": roof_s2, "strip": roof_strip}.get(key) or roof
+            out["roofline"] = None if chosen is None else dict(
+                chosen, selected_by=f"largest share of the training iteration among the probed (kernel, grid) instances in {STATS_FILE}: "
+                                     f"{pct} % ({key})",
+                stats_measured_on_this_tree=stats_current())
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_batch)
         _emit(json.dumps(out), out_fd)
     if dist_on:
         dist.barrier()   # the other ranks wait for rank 0's roofline probes, then everybody tears down together

@@ -197,7 +197,8 @@ extern "C" int dgv2_bmm_tn_cat(float* gw, const void* gy, const void* xa, const 
 // Weight gradient of the output heads: gw[b,o,i] = sum_p gy[b,p,o] x[b,p,i] with O <= 4 output channels (image,
 // ray-drop logit).  As a GEMM it fills 2 of 16 MFMA rows and ran at a quarter of the streaming rate; it is a
 // weighted column sum of x, so: a thread owns one 16-byte channel vector and a lane of pixels, partial sums meet
-// in LDS and leave as one fp32 atomic per (o, i) and block (gw cleared first; B * nsplit blocks).
+// in LDS and are stored by ONE block per sample (fixed summation order: the same bits every run).  Callers with few
+// samples and many pixels split the pixels over the batch dimension (a reshape) and sum the partial results.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(256) void bmm_tn_small_kernel(float* __restrict__ g
       const int v = c / VN, j = c - v * VN;
       float s = 0.f;
       for (int k = 0; k < lanes; ++k) s += red[(k * cvecs + v) * VN + j];
-      atomicAdd(&gw[((int64_t)b * O + o) * I + c], s);
+      gw[((int64_t)b * O + o) * I + c] = s;
     }
   }
 }
@@ -262,15 +263,8 @@ extern "C" int dgv2_bmm_tn_small(float* gw, const void* gy, const void* x, int B
   if (!vn) return DGV2_EINVAL;
   if (O > 4 || I % vn || 256 % (I / vn) || !aligned16(x)) return DGV2_ENOTSUP;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(gw, 0, sizeof(float) * (size_t)B * O * I, st);
-  if (e != hipSuccess) return (int)e;
-  const int lanes = 256 / (I / vn);
-  int nsplit = (1024 + B - 1) / B;                       // ~1024 blocks
-  const int minpix = lanes * 16;                         // >= 16 pixels per thread
-  if ((int64_t)nsplit * minpix > P) nsplit = (P + minpix - 1) / minpix;
-  nsplit = nsplit < 1 ? 1 : nsplit;
-  const int ppb = (P + nsplit - 1) / nsplit;
-  dim3 grid((P + ppb - 1) / ppb, B);
+  const int ppb = P;                                     // one block per sample: no atomics, no zero fill
+  dim3 grid(1, B);
   DGV2_DISPATCH_DTYPE(dtype, {
     switch (O) {
       case 1: bmm_tn_small_kernel<T, 1><<<grid, 256, 0, st>>>(gw, (const T*)gy, (const T*)x, P, I, ppb); break;

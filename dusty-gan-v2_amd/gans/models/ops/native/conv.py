@@ -302,6 +302,24 @@ _TN_SCRATCH = {}
 _LIB_WGRAD = os.environ.get("DGV2_NO_LIB_WGRAD") is None         # A/B switch for benchmarking
 
 
+def _bmm_tn_small(gy, x, B, P, I, O, batch_sum=False):
+    """gw fp32 [B, O, I] = per-sample gy^T x for O <= 4 output channels (gy [B, P, O], x [B, P, I], contiguous, same
+    dtype), or its sum over the batch [O, I] (batch_sum); None where dgv2_bmm_tn_small does not apply.  The kernel runs
+    ONE block per batch entry and stores its sums (the same bits every run), so every caller goes through here: each
+    sample's P pixels go in as ns entries of P / ns pixels (a reshape), ns doubling while fewer than ~1024 blocks run
+    and each thread keeps >= 16 pixels, and the ns parts are summed in a fixed order."""
+    lanes = 256 // max(I * x.element_size() // 16, 1)
+    ns = 1
+    while B * ns < 1024 and P % (2 * ns) == 0 and P // (2 * ns) >= lanes * 16:
+        ns *= 2
+    parts = torch.empty((B, ns, O, I), device=x.device, dtype=torch.float32)
+    if not N.try_call("dgv2_bmm_tn_small", N.ptr(parts), N.ptr(gy), N.ptr(x), B * ns, P // ns, I, O, _dt(x), N.stream()):
+        return None
+    if batch_sum:
+        return parts.sum(dim=(0, 1))
+    return parts.view(B, O, I) if ns == 1 else parts.sum(dim=1)
+
+
 def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
     """gw fp32 [O,kh,kw,C].  gscale: return scale * gw as a PERMUTED VIEW of a contiguous [O,C,kh,kw] buffer (the
     parameter's layout): the permute-backward of a weight handle then hands the optimizer a contiguous gradient.
@@ -359,9 +377,9 @@ def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
         # 1x1 conv of a <= 4-channel input (the discriminator's stem when it runs as composable ops: R1): the weight
         # gradient is the heads' streaming column sum with the operands' roles swapped -- per[b, c, o] = sum_p
         # x[b, p, c] gy[b, p, o] -- instead of a GEMM with 2 of its 16 rows in use (277 -> ~20 us at B = 64)
-        per = torch.empty((B, C, O), device=x.device, dtype=torch.float32)
-        if N.try_call("dgv2_bmm_tn_small", N.ptr(per), N.ptr(x), N.ptr(gy), B, H * W, O, C, _dt(x), N.stream()):
-            gw.copy_(per.sum(dim=0).t().reshape(O, 1, 1, C))
+        per = _bmm_tn_small(x, gy, B, H * W, O, C, batch_sum=True)     # [C, O], summed over the batch
+        if per is not None:
+            gw.copy_(per.t().reshape(O, 1, 1, C))
             return gw
     N.call("dgv2_conv_wgrad", N.ptr(gw), N.ptr(gy), N.ptr(x), B, H, W, C, O, g.kh, g.kw, g.stride, g.pad, g.ring,
            _dt(x), N.stream())

@@ -397,9 +397,10 @@ class _ModUpPrepared(Function):
         elif cfg["act"] and gy.dtype == dt and Otot % vn == 0 and 256 % (Otot // vn) == 0:
             gpre = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
             gb = torch.empty(Otot, device=dev, dtype=torch.float32)
-            scratch = torch.empty(2048 * Otot, device=dev, dtype=torch.float32) if rows >= 65536 else None
+            # partial column sums + fold kernel at every size: the bias gradient is the same bits every run
+            scratch = torch.empty(2048 * Otot, device=dev, dtype=torch.float32)
             N.call("dgv2_bias_act_bwd_rs", N.ptr(gpre), N.ptr(gb), N.ptr(gy), N.ptr(out), rows, Otot, cfg["alpha"],
-                   cfg["scale"], N.ptr(cvec), N.ptr(scratch), 0 if scratch is None else scratch.numel(), _dt(gy),
+                   cfg["scale"], N.ptr(cvec), N.ptr(scratch), scratch.numel(), _dt(gy),
                    N.stream())
             if not cfg["has_bias"]:
                 gb = None

@@ -415,9 +415,10 @@ class _ModGemmPrepared(Function):
             pass
         elif cfg["act"] and gy.dtype == dt and Otot % vn == 0 and 256 % (Otot // vn) == 0:
             gb = torch.empty(Otot, device=dev, dtype=torch.float32)
-            scratch = torch.empty(2048 * Otot, device=dev, dtype=torch.float32) if rows >= 65536 else None
+            # partial column sums + fold kernel at every size: the bias gradient is the same bits every run
+            scratch = torch.empty(2048 * Otot, device=dev, dtype=torch.float32)
             N.call("dgv2_bias_act_bwd_rs", N.ptr(gpre), N.ptr(gb), N.ptr(gy), N.ptr(out), rows, Otot, cfg["alpha"],
-                   cfg["scale"], N.ptr(cvec), N.ptr(scratch), 0 if scratch is None else scratch.numel(), _dt(gy),
+                   cfg["scale"], N.ptr(cvec), N.ptr(scratch), scratch.numel(), _dt(gy),
                    N.stream())
             if not cfg["has_bias"]:
                 gb = None
@@ -526,10 +527,11 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
         return gwb
     if _TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
         return _bmm_tn_stream(g3, xa, B, H, W_, I, Otot)
+    if Otot <= 4 and g3.dtype == xa.dtype:
+        gwb = _bmm_tn_small(g3, xa, B, P, I, Otot)   # the output heads: streaming weighted column sum
+        if gwb is not None:
+            return gwb
     gwb = torch.empty((B, Otot, I), device=g3.device, dtype=torch.float32)
-    if Otot <= 4 and g3.dtype == xa.dtype and N.try_call("dgv2_bmm_tn_small", N.ptr(gwb), N.ptr(g3), N.ptr(xa), B, P, I,
-                                                         Otot, _dt(xa), N.stream()):
-        return gwb   # the output heads: streaming weighted column sum
     N.call("dgv2_bmm_tn", N.ptr(gwb), N.ptr(g3), N.ptr(xa.reshape(B, P, I)), B, P, I, Otot, Otot, I, _dt(xa), N.stream())
     return gwb
 

@@ -297,7 +297,8 @@ int dgv2_bmm_nn_cat_sq(void* y, const void* xa, const void* xs, const void* w, i
 int dgv2_bmm_tn_cat(float* gw, const void* gy, const void* xa, const void* xs, int B, int P, int Ka, int Ks,
                     int O, int dtype, void* stream);
 /* The same per-sample weight gradient for O <= 4 output channels (the generator's output heads, dusty_v2.py:32-57):
- * a streaming weighted column sum instead of a 2-of-16-rows GEMM.  DGV2_ENOTSUP outside its shapes. */
+ * a streaming weighted column sum instead of a 2-of-16-rows GEMM, one block per sample (the same bits every run:
+ * split long pixel ranges over B and sum the parts).  DGV2_ENOTSUP outside its shapes. */
 int dgv2_bmm_tn_small(float* gw, const void* gy, const void* x, int B, int P, int I, int O, int dtype,
                       void* stream);
 /* ... and their data gradient y[b,p,k] = sum_{o<O} x[b,p,o] w[b,k,o] (+ resid), a contraction of O <= 4 terms. */

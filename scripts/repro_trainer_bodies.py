@@ -1,7 +1,8 @@
 """Bit-reproducibility of the captured step bodies at the timed configuration (64x512, bf16, B = 64): g_fb, d_fb and r1_fb
 are replayed K times (hipGraph replays, then eagerly) from IDENTICAL weights, buffers and injected draws, and the flat
-gradient buffer of every replay is compared with the first one, parameter by parameter.  Float atomics move a few
-tensors by ~1e-7 of their maximum; anything larger, or anything in a tensor no atomic touches, is a race.
+gradient buffer of every replay is compared with the first one, parameter by parameter.  No reduction of these bodies
+uses float atomics any more (the small-map bias gradients and the small weight gradients fold partial sums in a fixed
+order): every replay must match the first bit for bit, and a difference is a race.
 usage: repro_trainer_bodies.py [K=60]"""
 import copy, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -589,6 +589,26 @@ def test_bmm_tn_small_head_weight_gradient(nat, dtype, tol, B, P, I, O):
     assert_rel(gw.cpu(), want, tol)
 
 
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-5), (torch.bfloat16, 2e-3)])
+def test_small_weight_gradients_split_over_the_batch(nat, dtype, tol):
+    """native._bmm_tn_small feeds each sample's pixels to the one-block-per-entry kernel as several batch entries and
+    sums the parts (B = 4 with 32768 pixels: at least two parts per sample); the heads' weight gradient (_mod_wgrad)
+    and the <= 4-channel stem's in R1 (_conv_wgrad_raw) against fp64 einsums."""
+    g = torch.Generator().manual_seed(13)
+    B, H, W, I, O = 4, 64, 512, 32, 2
+    xa = torch.randn(B, H, W, I, generator=g).to(DEV).to(dtype)
+    g3 = torch.randn(B, H * W, O, generator=g).to(DEV).to(dtype)
+    gwb = nat._mod_wgrad(g3, xa, None, B, H, W, I, O, dtype)
+    assert tuple(gwb.shape) == (B, O, I)
+    want = torch.einsum("bpo,bpi->boi", g3.double().cpu(), xa.reshape(B, H * W, I).double().cpu())
+    assert_rel(gwb.cpu(), want, tol, "heads")
+    x = torch.randn(B, H, W, O, generator=g).to(DEV).to(dtype)     # stem input: O = 2 channels, gy: I = 32
+    gw = nat._conv_wgrad_raw(xa, x, nat.ConvGeom(1, 1, 1, 0, True))
+    assert tuple(gw.shape) == (I, 1, 1, O)
+    want = torch.einsum("bpo,bpc->oc", xa.reshape(B, H * W, I).double().cpu(), x.reshape(B, H * W, O).double().cpu())
+    assert_rel(gw.reshape(I, O).cpu(), want, tol, "stem")
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-6), (torch.bfloat16, 8e-3)])
 @pytest.mark.parametrize("B,P,O,K,with_resid", [(3, 1000, 2, 32, True), (2, 70, 1, 64, False), (2, 300, 4, 512, True)])
 def test_bmm_nn_small_head_data_gradient(nat, dtype, tol, B, P, O, K, with_resid):

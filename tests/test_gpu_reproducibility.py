@@ -156,3 +156,25 @@ def test_modconv_up_chain(nat, Ka, O):
         return pre[0], pre[1], pre[2]
 
     _same(run, 100)
+
+
+@pytest.mark.parametrize("rows,C", [(16384, 512), (32768, 256), (8192, 512)])
+def test_bias_gradient_below_65536_rows(nat, rows, C):
+    """Fused bias + leaky-ReLU backward at the small maps (D's 4 x 32 / 8 x 64 blocks, R1 at B = 64, G's level 1):
+    per-block column sums folded by the reduce kernel at every size.  The fp32-atomic form moved these bias gradients
+    by ~4e-7 from run to run, and through the bf16 trunks a few training iterations spread that over every weight."""
+    g = torch.Generator().manual_seed(11)
+    gy = torch.randn(rows, C, generator=g).to(DEV).bfloat16()
+    out = torch.randn(rows, C, generator=g).to(DEV).bfloat16()
+    _same(lambda: nat._BiasActBackward.apply(gy, out, True, 0.2, math.sqrt(2.0), 1, C))
+
+
+def test_small_weight_gradients(nat):
+    """dgv2_bmm_tn_small, one block per batch entry, with the pixels split over the batch: the weight gradient of the
+    <= 4-channel discriminator stem (R1's composable form) and of the generator's output heads."""
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn(64, 64, 512, 2, generator=g).to(DEV).bfloat16()
+    gy = torch.randn(64, 64, 512, 32, generator=g).to(DEV).bfloat16()
+    _same(lambda: nat._conv_wgrad_raw(gy, x, nat.ConvGeom(1, 1, 1, 0, True)))
+    g3 = torch.randn(64, 64 * 512, 2, generator=g).to(DEV).bfloat16()
+    _same(lambda: nat._mod_wgrad(g3, gy, None, 64, 64, 512, 32, 2, torch.bfloat16))
