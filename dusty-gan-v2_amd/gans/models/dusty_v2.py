@@ -798,7 +798,7 @@ class Discriminator(nn.Module):
     def _weight_bank(self):
         """Compute-dtype copies of every ResidualBlock / epilogue conv weight (forward and data-gradient layouts)
         in ONE launch per pass instead of ~5 tiny scale / permute / cast launches per conv (first-order passes
-        only; uniform precision only).  {conv: (scale, cpad, wf, wt)}."""
+        only; uniform precision only).  {conv: native.PreparedConv}."""
         if self.num_fp16_layers not in (-1, 0):
             return None
         dt = LOW if self.num_fp16_layers == -1 else torch.float32
@@ -820,11 +820,11 @@ class Discriminator(nn.Module):
         # (the fp32 parity mode keeps its convs on the exact fp32 MFMA: no images)
         prepared = native.conv_weight_bank([e for _, e in items], dt,
                                            image8=[dt == LOW and (True if m.geom.stride == 1 else "fwd") for m, _ in items])
-        bank = {m: (e[1], e[2], wf, wt, w8, w8t) for (m, e), (wf, wt, w8, w8t) in zip(items, prepared)}
+        bank = {m: native.PreparedConv(e[1], e[2], *images) for (m, e), images in zip(items, prepared)}
         if edt != dt:   # fp32 epilogue behind a reduced-precision trunk: its weight is prepared by a launch of its own
             # ... with the three-plane bf16 images of conv_x3.hip (fp32 on the bf16 matrix cores) where the shape allows
-            (wf, wt, w8, w8t), = native.conv_weight_bank([epi[1]], edt, image8=[True])
-            bank[conv] = (epi[1][1], epi[1][2], wf, wt, w8, w8t)
+            images, = native.conv_weight_bank([epi[1]], edt, image8=[True])
+            bank[conv] = native.PreparedConv(epi[1][1], epi[1][2], *images)
         return bank
 
     def _fp8_bank(self):

@@ -163,29 +163,24 @@ class Conv2d(nn.Sequential):
     def forward_cl(self, x, pad_in_to=None, act=None, geom=None, act_scale=None, resid=None, wscale=None, bank=None,
                    fork=False, down=None, fp8=None, q8=False):
         """act: a FusedLeakyReLU module fused into the conv epilogue; geom overrides the stride
-        (used when the caller has already decimated the input).  bank: {conv: (scale, cpad, wf, wt)} from
-        Discriminator's weight bank: the prepared compute-dtype weights ride along on `w` (which stays the
-        differentiable fp32 handle) when they were built with this call's scale and padding.
+        (used when the caller has already decimated the input).  bank: {conv: native.PreparedConv} from
+        Discriminator's weight bank: the record rides along on `w` (which stays the differentiable fp32 handle) as
+        `w._dgv2_bank` when it was built with this call's scale and padding.
         fp8 = (w8, descale) from native.fp8_quant_weights: `x` is then (bf16 handle, e4m3 payload) and the contraction
         runs on e4m3 operands (native.fp8); q8 (with `down`): the blurred activation leaves as such a pair."""
         geom = self.geom if geom is None else geom
         ent = None if bank is None else bank.get(self)
         if ent is not None:
             p_raw, s_used, cpad_used = self.bank_entry(wscale, pad_in_to)
-            if abs(ent[0] - s_used) <= 1e-12 * abs(s_used) and ent[1] == cpad_used:
+            if abs(ent.scale - s_used) <= 1e-12 * abs(s_used) and ent.cpad == cpad_used:
                 # the kernels read the bank's prepared copies; `w` only carries the autograd edge to the parameter
                 if cpad_used == p_raw.shape[1]:
                     # a free view of the parameter: the weight-gradient kernel writes scale * gw in the parameter's
                     # own layout, so the permute-backward of this view is the finished gradient (no launch)
                     w = p_raw.permute(0, 2, 3, 1)
-                    w._dgv2_handle, w._dgv2_gscale = True, float(s_used)
+                    w._dgv2_bank = (ent, float(s_used))
                 else:
-                    w = native.scaled_handle(p_raw, s_used, cpad_used)
-                w._dgv2_wf, w._dgv2_wt = ent[2], ent[3]
-                w._dgv2_w8 = ent[4] if len(ent) > 4 else None   # conv8.hip's staging images of the same values
-                w._dgv2_w8t = ent[5] if len(ent) > 5 else None
-                if w._dgv2_w8t is not None:
-                    w._dgv2_w8t._dgv2_clive = int(p_raw.shape[1])   # input channels before padding (conv_x3's data gradient)
+                    w = native.scaled_handle(p_raw, s_used, cpad_used, bank=ent)
                 b, gain = self._params_bias()
             else:
                 ent = None

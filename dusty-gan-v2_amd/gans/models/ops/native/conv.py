@@ -6,6 +6,7 @@ parts import each other in order, every name stays reachable as native.<name>.
 import math
 import contextlib
 import os
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -25,6 +26,11 @@ class ConvGeom:
 
     def out_hw(self, H, W):
         return (H + 2 * self.pad - self.kh) // self.stride + 1, (W + 2 * self.pad - self.kw) // self.stride + 1
+
+    @property
+    def ring3x3(self):
+        """3x3, pad 1, ring padding: the shape the eight-wave and plane-image engines take (the stride is the caller's test)."""
+        return bool(self.ring) and (self.kh, self.kw, self.pad) == (3, 3, 1)
 
 
 def _kstep(t):
@@ -127,16 +133,13 @@ def _conv_fwd_raw(x, w, g, bias=None, act=0, alpha=0.2, scale=1.0, resid=None, w
     Ho, Wo = g.out_hw(H, W)
     N.check(x, w, bias)
     y = torch.empty((B, Ho, Wo, O), device=x.device, dtype=x.dtype)
-    if (w8 is not None and _CONV8_IMG and x.dtype == torch.bfloat16 and g.ring and (g.kh, g.kw, g.pad) == (3, 3, 1)
-            and g.stride in (1, 2) and N.try_call("dgv2_conv3x3_fwd8", N.ptr(y), N.ptr(x), N.ptr(w8), B, H, W, C, O,
-                                                   g.stride, N.ptr(bias), N.ptr(resid), act, alpha, scale, _dt(x),
-                                                   N.stream())):
+    if (w8 is not None and _CONV8_IMG and x.dtype == torch.bfloat16 and g.ring3x3 and g.stride in (1, 2)
+            and N.try_call("dgv2_conv3x3_fwd8", N.ptr(y), N.ptr(x), N.ptr(w8), B, H, W, C, O, g.stride, N.ptr(bias),
+                           N.ptr(resid), act, alpha, scale, _dt(x), N.stream())):
         return y
-    if (w8 is None and _X3_AUTO[0] and x.dtype == torch.float32 and g.ring and (g.kh, g.kw, g.pad, g.stride) == (3, 3, 1, 1)
-            and W % 32 == 0):
+    if w8 is None and _X3_AUTO[0] and x.dtype == torch.float32 and g.ring3x3 and g.stride == 1 and W % 32 == 0:
         w8 = _x3_auto_images(w, True)
-    if (w8 is not None and _CONV_X3 and x.dtype == torch.float32 and w8.dtype == torch.bfloat16 and g.ring
-            and (g.kh, g.kw, g.pad, g.stride) == (3, 3, 1, 1)
+    if (w8 is not None and _CONV_X3 and x.dtype == torch.float32 and w8.dtype == torch.bfloat16 and g.ring3x3 and g.stride == 1
             and N.try_call("dgv2_conv3x3_x3_fwd", N.ptr(y), N.ptr(x), N.ptr(w8), B, H, W, C, min(int(xexact), C), O, N.ptr(bias),
                            N.ptr(resid), act, alpha, scale, N.ptr(N.status_word(x.device)), N.stream())):
         return y     # fp32 on the bf16 matrix cores (three-plane split, six products per multiply: conv_x3.hip)
@@ -240,14 +243,14 @@ def _conv_dgrad_raw(gy, w, g, xshape, wt=None, resid=None, w8t=None):
     the conv's channel count before padding rides on the image as _dgv2_clive)."""
     B, H, W, C = xshape
     O = gy.shape[3]
-    if (w8t is not None and _CONV8_IMG and gy.dtype == torch.bfloat16 and g.ring and (g.kh, g.kw, g.pad, g.stride) == (3, 3, 1, 1)
+    if (w8t is not None and _CONV8_IMG and gy.dtype == torch.bfloat16 and g.ring3x3 and g.stride == 1
             and w8t.dtype == gy.dtype):
         N.check(gy, w8t, resid)
         gx = _conv_dgrad8(gy, w8t, xshape, resid)
         if gx is not None:
             return gx
     if (w8t is not None and _CONV_X3 and gy.dtype == torch.float32 and w8t.dtype == torch.bfloat16 and wt is not None
-            and g.ring and (g.kh, g.kw, g.pad, g.stride) == (3, 3, 1, 1) and getattr(w8t, "_dgv2_clive", None)):
+            and g.ring3x3 and g.stride == 1 and getattr(w8t, "_dgv2_clive", None)):
         clive = w8t._dgv2_clive
         N.check(gy, w8t, wt, resid)
         gx = torch.empty(xshape, device=gy.device, dtype=gy.dtype)
@@ -255,14 +258,14 @@ def _conv_dgrad_raw(gy, w, g, xshape, wt=None, resid=None, w8t=None):
                       N.ptr(resid), N.stream()):
             return gx
     if wt is None:   # cached on the values tensor (see modgemm._values): first and second pass of R1 share it
-        c = getattr(w, "_dgv2_wt", None)
+        c = getattr(w, "_dgv2_vals_t", None)
         if c is not None and c[0] == w._version:
             wt = c[1]
         else:
             wt = w.permute(3, 1, 2, 0).contiguous()
-            w._dgv2_wt = (w._version, wt)
+            w._dgv2_vals_t = (w._version, wt)
     N.check(gy, wt, resid)
-    if (w is not None and _X3_AUTO[0] and gy.dtype == torch.float32 and g.ring and (g.kh, g.kw, g.pad, g.stride) == (3, 3, 1, 1)
+    if (w is not None and _X3_AUTO[0] and gy.dtype == torch.float32 and g.ring3x3 and g.stride == 1
             and W % 32 == 0 and H >= 2 and C % 64 <= 16):
         w3t = _x3_auto_images(w, False)      # (padding channels, if any, are weights of zero: their gradient comes out as 0)
         if w3t is not None:
@@ -331,7 +334,7 @@ def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
     N.check(gy, x)
     if x3 is None and _X3_AUTO[0]:
         x3 = int(_X3_AUTO[1].get(C, C))
-    if (x3 and _CONV_X3 and x.dtype == torch.float32 and g.ring and (g.kh, g.kw, g.pad, g.stride) == (3, 3, 1, 1)
+    if (x3 and _CONV_X3 and x.dtype == torch.float32 and g.ring3x3 and g.stride == 1
             and O % 128 == 0 and C >= 64 and C % 8 == 0 and W % 32 == 0 and 0 <= x3 - C // 64 * 64 <= 16):
         key = ("x3", B, H, W, C, int(x3), O)
         if key not in _WGRAD_SCRATCH:
@@ -355,8 +358,7 @@ def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
               torch.empty((O, C, g.kh, g.kw), device=x.device, dtype=torch.float32))
     else:
         gw = torch.empty((O, g.kh, g.kw, C), device=x.device, dtype=torch.float32)
-    if _WGRAD_STREAM and g.kh == g.kw and (g.kh, g.pad) in ((3, 1), (1, 0)) and g.stride in (1, 2) \
-            and C % (16 // x.element_size()) == 0 and O % (16 // x.element_size()) == 0:
+    if stream_ok:
         key = (B, H, W, C, O, g.kh, g.stride, g.pad, _dt(x))
         if key not in _WGRAD_SCRATCH:
             n = _ct.c_int64(0)
@@ -386,19 +388,45 @@ def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
     return gw
 
 
-def _bank(w, x):
-    """(forward-layout, transposed) compute-dtype weights prepared by conv_weight_bank for this call, or (None, None)."""
-    wf, wt = getattr(w, "_dgv2_wf", None), getattr(w, "_dgv2_wt", None)
-    if wf is not None and wf.dtype == x.dtype:
-        return wf, wt
-    return None, None
+class PreparedConv(NamedTuple):
+    """One conv weight as conv_weight_bank prepared it for a pass (Discriminator._weight_bank: {conv: PreparedConv}):
+    the runtime scale and padded input channel count it was built with, the compute-dtype values in the forward [O,kh*kw,cpad]
+    and transposed [cpad,kh*kw,O] layouts, and the staging images of the same values where the shape has them."""
+    scale: float
+    cpad: int
+    wf: torch.Tensor
+    wt: torch.Tensor
+    w8: Optional[torch.Tensor] = None
+    w8t: Optional[torch.Tensor] = None
 
 
-def _bank8(w, x):
-    """The bank's staging image for the eight-wave forward conv (same values as the forward layout), or None."""
-    w8 = getattr(w, "_dgv2_w8", None)
-    ok = w8 is not None and (w8.dtype == x.dtype or (x.dtype == torch.float32 and w8.dtype == torch.bfloat16))   # fp32: conv_x3's planes
-    return w8 if (ok and getattr(w, "_dgv2_wf", None) is not None) else None
+def _weights(ctx, w, x):
+    """What every conv Function's forward starts with: -> (weights in x's dtype [O,kh,kw,C], the forward staging image
+    or None) for _conv_fwd_raw, and ctx.bank = (wt, w8t, gscale) for _conv_grads.  A weight handle carries ONE attribute,
+    _dgv2_bank = (PreparedConv, gscale: see _ConvDgrad), put there by Conv2d.forward_cl / scaled_handle: the weights come
+    from its record when that was prepared in x's dtype, else from the tensor's own values (a handle has none: _values
+    raises)."""
+    rec, gscale = getattr(w, "_dgv2_bank", (None, None))
+    if rec is None or rec.wf.dtype != x.dtype:
+        ctx.bank = (None, None, gscale)
+        return _values(w, x.dtype).reshape(w.shape), None
+    ctx.bank = (rec.wt, rec.w8t, gscale)
+    return rec.wf.reshape(w.shape), rec.w8   # (an fp32 record's images are conv_x3.hip's bf16 planes)
+
+
+def _conv_grads(ctx, gy, x, w, g, want_gw, resid=None, xexact=0):
+    """(gx [+ resid], gw) of a conv Function whose forward ran _weights; each is None where it is not asked for
+    (want_gw: the class's own guard for the weight gradient)."""
+    wt, w8t, gscale = ctx.bank
+    gx = _dgrad(gy, w, g, tuple(x.shape), wt, resid, gscale, w8t) if ctx.needs_input_grad[0] else None
+    if not want_gw:
+        return gx, None
+    # the conv ran on conv_x3.hip's plane images (fp32 behind the weight bank): its weight gradient does too; x3 = the
+    # conv's input channel count before padding
+    x3 = None
+    if gy.dtype == torch.float32 and w8t is not None and w8t.dtype == torch.bfloat16:
+        x3 = getattr(w8t, "_dgv2_clive", None)
+    return gx, _ConvWgrad.apply(gy, x, g, gscale, x3, xexact, _wgrad_out(w, gscale))
 
 
 class _ConvFwd(Function):
@@ -406,24 +434,17 @@ class _ConvFwd(Function):
     def forward(ctx, x, w, g):
         ctx.set_materialize_grads(False)   # an absent cotangent stays absent (see _ConvAct)
         x = x.contiguous()
-        wc, ctx.wt = _bank(w, x)
-        ctx.w8t = getattr(w, "_dgv2_w8t", None) if ctx.wt is not None else None
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
-        if wc is None:
-            wc = _values(w, x.dtype)
+        wc, w8 = _weights(ctx, w, x)
         ctx.save_for_backward(x, w)
         ctx.g = g
-        return _conv_fwd_raw(x, wc.reshape(w.shape), g, w8=_bank8(w, x))
+        return _conv_fwd_raw(x, wc, g, w8=w8)
 
     @staticmethod
     def backward(ctx, gy):
         if gy is None:
             return None, None, None
         x, w = ctx.saved_tensors
-        gx = _dgrad(gy, w, ctx.g, tuple(x.shape), ctx.wt, None, ctx.gscale, ctx.w8t) if ctx.needs_input_grad[0] else None
-        gw = (_ConvWgrad.apply(gy, x, ctx.g, ctx.gscale, _x3_hint(ctx, gy), 0, _wgrad_out(w, ctx.gscale))
-              if want_param_grad(ctx, 1) else None)
-        return gx, gw, None
+        return _conv_grads(ctx, gy, x, w, ctx.g, want_param_grad(ctx, 1)) + (None,)
 
 
 def _dgrad(gy, w, g, xshape, wt=None, resid=None, gscale=None, w8t=None):
@@ -454,15 +475,6 @@ class _ConvDgrad(Function):
         g_gy = _ConvFwd.apply(ggx, w, ctx.g) if ctx.needs_input_grad[0] else None
         g_w = _ConvWgrad.apply(gy, ggx, ctx.g, ctx.gscale) if ctx.needs_input_grad[1] else None
         return g_gy, g_w, None, None, None, (ggx if ctx.needs_input_grad[5] else None), None, None
-
-
-def _x3_hint(ctx, gy):
-    """The conv ran on conv_x3.hip's plane images (fp32 behind the weight bank): its weight gradient does too; -> the
-    conv's input channel count before padding, or None."""
-    w8t = getattr(ctx, "w8t", None)
-    if gy.dtype == torch.float32 and w8t is not None and w8t.dtype == torch.bfloat16:
-        return getattr(w8t, "_dgv2_clive", None)
-    return None
 
 
 def _wgrad_out(w, gscale):
@@ -518,13 +530,8 @@ class _ConvAct(Function):
         # channels [0, n) of x are bf16-representable -- conv_x3.hip skips their zero planes (forward, weight gradient)
         ctx.x_exact = int(getattr(x, "_dgv2_exact", 0))
         x = x.contiguous()
-        wc, ctx.wt = _bank(w, x)
-        ctx.w8t = getattr(w, "_dgv2_w8t", None) if ctx.wt is not None else None
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
-        if wc is None:
-            wc = _values(w, x.dtype)
-        out = _conv_fwd_raw(x, wc.reshape(w.shape), g, bias.detach().float().contiguous(), 3, alpha, scale, w8=_bank8(w, x),
-                            xexact=ctx.x_exact)
+        wc, w8 = _weights(ctx, w, x)
+        out = _conv_fwd_raw(x, wc, g, bias.detach().float().contiguous(), 3, alpha, scale, w8=w8, xexact=ctx.x_exact)
         ctx.save_for_backward(x, w, out)
         ctx.cfg = (g, alpha, scale, bias.numel())
         return out
@@ -536,9 +543,7 @@ class _ConvAct(Function):
         x, w, out = ctx.saved_tensors
         g, alpha, scale, size_b = ctx.cfg
         gpre, gb = _BiasActBackward.apply(gy, out, want_param_grad(ctx, 2), alpha, scale, 1, size_b)
-        gx = _dgrad(gpre, w, g, tuple(x.shape), ctx.wt, None, ctx.gscale, ctx.w8t) if ctx.needs_input_grad[0] else None
-        gw = (_ConvWgrad.apply(gpre, x, g, ctx.gscale, _x3_hint(ctx, gpre), ctx.x_exact, _wgrad_out(w, ctx.gscale))
-              if want_param_grad(ctx, 1) else None)
+        gx, gw = _conv_grads(ctx, gpre, x, w, g, want_param_grad(ctx, 1), xexact=ctx.x_exact)
         return gx, gw, gb, None, None, None
 
 
@@ -903,9 +908,10 @@ class _ScaledHandle(Function):
         return torch.mul(gp, ctx.scale, out=out), None, None
 
 
-def scaled_handle(param, scale, cpad=0):
+def scaled_handle(param, scale, cpad=0, bank=None):
+    """bank: the PreparedConv whose copies stand in for the handle's values (without one, any use of the values raises)."""
     h = _ScaledHandle.apply(param, float(scale), int(cpad))
-    h._dgv2_handle = True
+    h._dgv2_bank = (bank, None)
     return h
 
 
@@ -936,42 +942,21 @@ def convx3t_image_ok(p, cpad, dtype):
 
 def conv_weight_bank(entries, dtype, image8=None):
     """entries: list of (param fp32 [O,C,kh,kw], scale, Cpad).  One launch; returns [(wf [O,kh*kw,Cpad], wt
-    [Cpad,kh*kw,O])] in `dtype` (views of two flat buffers).  image8: list of bools -- also write the staging image of
-    the eight-wave forward conv (and of its stride-1 data gradient) for those layers (dgv2_conv_weight_bank_ex); the
-    result tuples then are (wf, wt, w8 or None, w8t or None)."""
-    if image8 is not None:
-        return _conv_weight_bank8(entries, dtype, image8)
+    [Cpad,kh*kw,O])] in `dtype` (views of two flat buffers).  image8: list of flags -- also write the staging image of
+    the eight-wave forward conv (True: and of its stride-1 data gradient; "fwd": the forward one only, stride-2 convs have
+    no stride-1 data gradient) for those layers where the shape allows (dgv2_conv_weight_bank_ex); the result tuples then
+    are (wf, wt, w8 or None, w8t or None).  fp32 layers get conv_x3.hip's three-plane bf16 images instead; a transposed
+    plane image carries the conv's channel count before padding as _dgv2_clive (_conv_dgrad_raw)."""
     L = len(entries)
     dev = entries[0][0].device
     dims = [(p.shape[0], p.shape[1], int(cp), p.shape[2] * p.shape[3]) for p, _, cp in entries]
     sizes = [o * kk * cp for o, _, cp, kk in dims]
     flat_f = torch.empty(sum(sizes), device=dev, dtype=dtype)
     flat_t = torch.empty(sum(sizes), device=dev, dtype=dtype)
-    wfs, wts, off = [], [], 0
-    for (o, c, cp, kk), n in zip(dims, sizes):
-        wfs.append(flat_f[off:off + n].view(o, kk, cp))
-        wts.append(flat_t[off:off + n].view(cp, kk, o))
-        off += n
-    srcs = [p.detach() for p, _, _ in entries]
-    N.check(*srcs)
-    N.call("dgv2_conv_weight_bank", _ptr_array(wfs), _ptr_array(wts), _ptr_array(srcs), _int_array([d[0] for d in dims]),
-           _int_array([d[1] for d in dims]), _int_array([d[2] for d in dims]), _int_array([d[3] for d in dims]),
-           (_ct.c_float * L)(*[float(s) for _, s, _ in entries]), L, N.dtype_code(flat_f), N.stream())
-    return list(zip(wfs, wts))
-
-
-def _conv_weight_bank8(entries, dtype, image8):
-    L = len(entries)
-    dev = entries[0][0].device
-    dims = [(p.shape[0], p.shape[1], int(cp), p.shape[2] * p.shape[3]) for p, _, cp in entries]
-    sizes = [o * kk * cp for o, _, cp, kk in dims]
-    flat_f = torch.empty(sum(sizes), device=dev, dtype=dtype)
-    flat_t = torch.empty(sum(sizes), device=dev, dtype=dtype)
-    # image8 entries: True = both images where the shape allows, "fwd" = only the forward one (stride-2 convs have no
-    # stride-1 data gradient).  fp32 layers get conv_x3.hip's three-plane bf16 images instead.
     x3 = dtype == torch.float32
-    want = [bool(f) and (convx3_image_ok if x3 else conv8_image_ok)(p, cp, dtype) for f, (p, _, cp) in zip(image8, entries)]
-    want_t = [f is True and (convx3t_image_ok if x3 else conv8t_image_ok)(p, cp, dtype) for f, (p, _, cp) in zip(image8, entries)]
+    flags = image8 if image8 is not None else [False] * L
+    want = [bool(f) and (convx3_image_ok if x3 else conv8_image_ok)(p, cp, dtype) for f, (p, _, cp) in zip(flags, entries)]
+    want_t = [f is True and (convx3t_image_ok if x3 else conv8t_image_ok)(p, cp, dtype) for f, (p, _, cp) in zip(flags, entries)]
     if x3:
         n8 = [3 * (o // 64) * ((cp + 31) // 32) * 2304 * 8 for o, _, cp, _ in dims]
         n8t = [3 * (cp // 64) * (o // 32) * 2304 * 8 for o, _, cp, _ in dims]
@@ -986,15 +971,20 @@ def _conv_weight_bank8(entries, dtype, image8):
         wts.append(flat_t[off:off + n].view(cp, kk, o))
         w8s.append(flat_8[off8:off8 + m8] if f else None)
         w8ts.append(flat_8t[off8t:off8t + m8t] if ft else None)
+        if ft and x3:
+            w8ts[-1]._dgv2_clive = int(c)
         off += n
         off8 += m8 if f else 0
         off8t += m8t if ft else 0
     srcs = [p.detach() for p, _, _ in entries]
     N.check(*srcs)
-    N.call("dgv2_conv_weight_bank_ex", _ptr_array(wfs), _ptr_array(wts), _ptr_array(w8s), _ptr_array(w8ts), _ptr_array(srcs),
-           _int_array([d[0] for d in dims]), _int_array([d[1] for d in dims]), _int_array([d[2] for d in dims]),
-           _int_array([d[3] for d in dims]), (_ct.c_float * L)(*[float(s) for _, s, _ in entries]), L,
-           N.dtype_code(flat_f), N.stream())
+    rest = (_ptr_array(srcs), _int_array([d[0] for d in dims]), _int_array([d[1] for d in dims]),
+            _int_array([d[2] for d in dims]), _int_array([d[3] for d in dims]),
+            (_ct.c_float * L)(*[float(s) for _, s, _ in entries]), L, N.dtype_code(flat_f), N.stream())
+    if image8 is None:
+        N.call("dgv2_conv_weight_bank", _ptr_array(wfs), _ptr_array(wts), *rest)
+        return list(zip(wfs, wts))
+    N.call("dgv2_conv_weight_bank_ex", _ptr_array(wfs), _ptr_array(wts), _ptr_array(w8s), _ptr_array(w8ts), *rest)
     return list(zip(wfs, wts, w8s, w8ts))
 
 
@@ -1007,12 +997,8 @@ class _ConvActFork(Function):
     def forward(ctx, x, w, bias, g, alpha, scale):
         ctx.set_materialize_grads(False)
         x = x.contiguous()
-        wc, ctx.wt = _bank(w, x)
-        ctx.w8t = getattr(w, "_dgv2_w8t", None) if ctx.wt is not None else None
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
-        if wc is None:
-            wc = _values(w, x.dtype)
-        out = _conv_fwd_raw(x, wc.reshape(w.shape), g, bias.detach().float().contiguous(), 3, alpha, scale, w8=_bank8(w, x))
+        wc, w8 = _weights(ctx, w, x)
+        out = _conv_fwd_raw(x, wc, g, bias.detach().float().contiguous(), 3, alpha, scale, w8=w8)
         ctx.save_for_backward(x, w, out)
         ctx.cfg = (g, alpha, scale, bias.numel())
         return out, x.view_as(x)
@@ -1024,9 +1010,7 @@ class _ConvActFork(Function):
         if gy is None:   # only the sibling branch carries a gradient
             return gx_sibling, None, None, None, None, None
         gpre, gb = _BiasActBackward.apply(gy, out, True, alpha, scale, 1, size_b)
-        gx = _dgrad(gpre, w, g, tuple(x.shape), ctx.wt, gx_sibling, ctx.gscale, ctx.w8t) if ctx.needs_input_grad[0] else None
-        gw = (_ConvWgrad.apply(gpre, x, g, ctx.gscale, _x3_hint(ctx, gpre), 0, _wgrad_out(w, ctx.gscale))
-              if ctx.needs_input_grad[1] else None)
+        gx, gw = _conv_grads(ctx, gpre, x, w, g, ctx.needs_input_grad[1], resid=gx_sibling)
         return gx, gw, gb, None, None, None
 
 
@@ -1087,12 +1071,8 @@ class _ConvActDown(Function):
         payload[, x])."""
         ctx.set_materialize_grads(False)
         x = x.contiguous()
-        wc, ctx.wt = _bank(w, x)
-        ctx.w8t = getattr(w, "_dgv2_w8t", None) if ctx.wt is not None else None
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
-        if wc is None:
-            wc = _values(w, x.dtype)
-        out = _conv_fwd_raw(x, wc.reshape(w.shape), g, bias.detach().float().contiguous(), 3, alpha, scale, w8=_bank8(w, x))
+        wc, w8 = _weights(ctx, w, x)
+        out = _conv_fwd_raw(x, wc, g, bias.detach().float().contiguous(), 3, alpha, scale, w8=w8)
         in_hw = (out.shape[1], out.shape[2])
         ctx.save_for_backward(x, w, out)
         ctx.cfg = (g, alpha, scale, bias.numel(), spec, in_hw)
@@ -1121,10 +1101,8 @@ class _ConvActDown(Function):
         else:   # composed (also the differentiable form for create_graph=True)
             gh = _Resample.apply(gy, spec, True, in_hw)
             gpre, gb = _BiasActBackward.apply(gh, out, True, alpha, scale, 1, size_b)
-        gx = _dgrad(gpre, w, g, tuple(x.shape), ctx.wt, gx_sibling, ctx.gscale, ctx.w8t) if ctx.needs_input_grad[0] else gx_sibling
-        gw = (_ConvWgrad.apply(gpre, x, g, ctx.gscale, _x3_hint(ctx, gpre), 0, _wgrad_out(w, ctx.gscale))
-              if ctx.needs_input_grad[1] else None)
-        return gx, gw, gb, None, None, None, None, None, None
+        gx, gw = _conv_grads(ctx, gpre, x, w, g, ctx.needs_input_grad[1], resid=gx_sibling)
+        return (gx if ctx.needs_input_grad[0] else gx_sibling), gw, gb, None, None, None, None, None, None
 
 
 def conv_ring_act_down(x, w, bias, geom, spec, alpha=0.2, scale=math.sqrt(2.0), fork=False, q8=False):
@@ -1140,23 +1118,17 @@ class _ConvResid(Function):
         ctx.set_materialize_grads(False)
         x = x.contiguous()
         resid = resid.contiguous()
-        wc, ctx.wt = _bank(w, x)
-        ctx.w8t = getattr(w, "_dgv2_w8t", None) if ctx.wt is not None else None
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
-        if wc is None:
-            wc = _values(w, x.dtype)
+        wc, w8 = _weights(ctx, w, x)
         ctx.save_for_backward(x, w)
         ctx.g = g
-        return _conv_fwd_raw(x, wc.reshape(w.shape), g, resid=resid, w8=_bank8(w, x))
+        return _conv_fwd_raw(x, wc, g, resid=resid, w8=w8)
 
     @staticmethod
     def backward(ctx, gy):
         if gy is None:
             return None, None, None, None
         x, w = ctx.saved_tensors
-        gx = _dgrad(gy, w, ctx.g, tuple(x.shape), ctx.wt, None, ctx.gscale, ctx.w8t) if ctx.needs_input_grad[0] else None
-        gw = (_ConvWgrad.apply(gy, x, ctx.g, ctx.gscale, _x3_hint(ctx, gy), 0, _wgrad_out(w, ctx.gscale))
-              if want_param_grad(ctx, 1) else None)
+        gx, gw = _conv_grads(ctx, gy, x, w, ctx.g, want_param_grad(ctx, 1))
         return gx, gw, (gy if ctx.needs_input_grad[2] else None), None
 
 

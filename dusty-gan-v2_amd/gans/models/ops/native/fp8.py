@@ -119,8 +119,8 @@ class _ConvAct8(Function):
     def forward(ctx, handle, x8, w, w8, descale, bias, g, alpha, scale):
         ctx.set_materialize_grads(False)
         out = _conv_fwd_fp8(x8, w8, descale, g, bias.detach().float().contiguous(), 3, alpha, scale)
-        ctx.wt = getattr(w, "_dgv2_wt", None)
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
+        rec, ctx.gscale = getattr(w, "_dgv2_bank", (None, None))   # conv._weights: the handle's one attribute
+        ctx.wt = None if rec is None else rec.wt
         ctx.save_for_backward(x8, w, out)
         ctx.cfg = (g, alpha, scale, bias.numel())
         return out
@@ -144,8 +144,8 @@ class _ConvResid8(Function):
     def forward(ctx, handle, x8, w, w8, descale, resid, g):
         ctx.set_materialize_grads(False)
         resid = resid.contiguous()
-        ctx.wt = getattr(w, "_dgv2_wt", None)
-        ctx.gscale = getattr(w, "_dgv2_gscale", None)
+        rec, ctx.gscale = getattr(w, "_dgv2_bank", (None, None))   # conv._weights: the handle's one attribute
+        ctx.wt = None if rec is None else rec.wt
         ctx.save_for_backward(x8, w)
         ctx.g = g
         return _conv_fwd_fp8(x8, w8, descale, g, resid=resid)

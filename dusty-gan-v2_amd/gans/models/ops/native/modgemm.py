@@ -521,7 +521,7 @@ _PE_FWD = os.environ.get("DGV2_NO_PE_FWD") is None               # A/B switch fo
 def _values(w, dtype):
     """Compute-dtype VALUES of a conv weight; a weight-bank handle has none (its prepared copies did not match
     this call: wrong dtype, or a second-order pass that must run with the bank off)."""
-    if getattr(w, "_dgv2_handle", False):
+    if getattr(w, "_dgv2_bank", None) is not None:   # (native.conv: what marks a handle)
         raise RuntimeError("conv weight handle without values: run this pass without the weight bank "
                            "(Discriminator.forward(double_backward=True))")
     # one conversion per weight tensor and pass: the second-order passes of R1 (bank off) use each effective weight in
