@@ -2,7 +2,8 @@
 
 The per-pixel laser-angle grid is resampled once on the host at construction (sin/cos, 3x
 circular tile, bilinear resize, atan2 -- coords.py:59-71); the conversions used on the training
-path run in dgv2_coords_convert (elementwise, HBM-bound, fp32)."""
+path run in dgv2_coords_convert (elementwise, HBM-bound, fp32); an input that requires grad records
+dgv2_coords_convert_bwd as its backward."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -65,6 +66,11 @@ class CoordBridge(nn.Module):
         raise NotImplementedError(f"{coord}")
 
     def _k(self, x, mode, mask=None, raydrop_const=-1.0, out=None):
+        if out is None and x.requires_grad and torch.is_grad_enabled():
+            # inversion differentiates the conversion (demo_inversion.py:169); the `out=` form (the trainer's static
+            # batch) stays a plain launch
+            return native.coords_convert_diff(x, mode, self.min_depth, self.max_depth, self.angle.contiguous(), mask,
+                                              raydrop_const)
         return native.coords_convert(x, mode, self.min_depth, self.max_depth, self.angle.contiguous(), mask,
                                      raydrop_const, out=out)
 

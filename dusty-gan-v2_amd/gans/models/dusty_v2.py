@@ -290,14 +290,8 @@ class SynthesisBlock(nn.Module):
                 a1 = self.bias_act1
                 up = dict(link=link if self.is_first else link1, alpha=float(a1.negative_slope), scale=float(a1.scale),
                           cvec=self.conv1._prep[2])
-        elif angle.requires_grad and torch.is_grad_enabled():
-            # differentiable encoding (gradients w.r.t. the angles: inversion / demo consumers; not the training path)
-            a = angle if shift is None else angle + torch.stack([torch.zeros_like(shift), shift], dim=1)[:, :, None, None]
-            c = torch.einsum("bahw,fa->bhwf", a.float(), self.pe.freqs2.float()) + self.pe.phase.float()
-            pe = torch.cat([c.sin(), c.cos()], dim=3).to(dt)
-            x1 = pe if hin is None else torch.cat([self.resample.forward_cl(hin), pe], dim=3)
-            h = self.conv1.forward_cl(x1, ws[0], act=self.bias_act1)
         else:
+            # (an angle grid that requires grad -- inversion: angle + phase -- gets its gradient from this node as well)
             x1 = native.up_cat_pe(hin, spec, angle, shift, self.pe.freqs2.contiguous(), self.pe.phase, dt, B)
             h = self.conv1.forward_cl(x1, ws[0], act=self.bias_act1)
         nxt = 1

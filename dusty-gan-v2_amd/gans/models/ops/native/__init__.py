@@ -17,3 +17,4 @@ from .stem_tail_ada import *  # noqa: F401,F403
 from .modlayer import *  # noqa: F401,F403
 from .misc import *  # noqa: F401,F403
 from .second_order import *  # noqa: F401,F403
+from .inversion import *  # noqa: F401,F403

@@ -12,6 +12,7 @@ from torch.autograd import Function
 
 import dgv2_native as N
 from .act_resample import *  # noqa: F401,F403
+from .inversion import fourier_feature_bwd
 
 
 # ---------------------------------------------------------------------------------------
@@ -314,18 +315,23 @@ class _UpCatPE(Function):
         x1 = torch.empty((B, H, W, Cin + F2), device=angle.device, dtype=dtype)
         if h is not None:
             _resample_raw(h, spec, False, (h.shape[1], h.shape[2]), out=x1, ldy=Cin + F2)
-        fourier_feature_into(x1, Cin, angle, shift, freqs2, phase)
+        angle_d = angle.detach().float().contiguous()
+        fourier_feature_into(x1, Cin, angle_d, shift, freqs2, phase)
         ctx.cfg = (spec, None if h is None else (h.shape[1], h.shape[2]), Cin)
+        # the angle gradient (inversion: demo_inversion.py:164 optimises angle + phase) recomputes the encoding from these
+        ctx.pe = (angle_d, shift, freqs2, phase) if ctx.needs_input_grad[2] else None
         return x1
 
     @staticmethod
     def backward(ctx, g):
         spec, in_hw, Cin = ctx.cfg
-        if in_hw is None:
-            return (None,) * 8
         g = g.contiguous()
-        gh = _resample_raw(g, spec, True, in_hw, ldx=g.shape[3], C=Cin)
-        return gh, None, None, None, None, None, None, None
+        gh = ga = None
+        if in_hw is not None and ctx.needs_input_grad[0]:
+            gh = _resample_raw(g, spec, True, in_hw, ldx=g.shape[3], C=Cin)
+        if ctx.pe is not None:
+            ga = fourier_feature_bwd(g, Cin, *ctx.pe)
+        return gh, None, ga, None, None, None, None, None
 
 
 def up_cat_pe(h, spec, angle, shift, freqs2, phase, dtype, B):

@@ -949,6 +949,46 @@ int dgv2_glin_dweight(float* const* dw, float* const* dbias, const float* const*
                       const float* const* x, const int* N, const int* ldx, int L, int B, int K, float alpha, float beta,
                       float slope, const float* rnorm, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * GAN inversion (inversion.hip).  All fp32, NCHW, ring convention of ops.Pad(1, "replicate", ring=True): circular
+ * along W, replicate along H; a level [Hi,Wi] pools to [(Hi+1)/2, (Wi+1)/2].  Every entry is ONE launch (one block per
+ * sample walks the levels; per-sample sums are fixed-order block reductions: run-to-run bit-identical, no atomics).
+ * L <= 16 levels; every pooled level has Wi >= 2.
+ *
+ * Target pyramid, once per target.  replaces: the ref / mask side of MultiScaleMaskedLoss.forward, update_mask and
+ *   blurpool, gans/inversion.py:45-76 (which recomputes it on every call).
+ * ref [B,C,H,W], mask [B,1,H,W] -> refp: levels 0 .. L-1 of ref ([B,C,Hi,Wi] each, level after level); maskp, normp:
+ * [B,Hi,Wi] per level in the same order (normp's level i is the norm that scales level i = 9 / window count of level
+ * i-1's mask, 9 where the count is 0; its level 0 is not written); invm [L,B] = 1 / (sum(mask_i) + 1e-8).
+ * ------------------------------------------------------------------------- */
+int dgv2_msml_prepare(float* refp, float* maskp, float* normp, float* invm, const float* ref, const float* mask, int B,
+                      int C, int H, int W, int L, void* stream);
+/* The loss: loss [B] = sum_i masked_loss(ref_i, gen_i, mask_i), gen_{i+1} = blurpool(gen_i mask_i) norm_{i+1}.
+ * replaces: masked_loss and the gen side of MultiScaleMaskedLoss.forward, gans/inversion.py:23-29,64-76 (without the
+ *   blurpool after the last level, whose result the reference discards).
+ * metric 0 = F.l1_loss, 1 = F.mse_loss; relative: (loss mask) / (ref + 1e-11), then mask again, as the reference.
+ * genp: levels 1 .. L-1 of the generated pyramid (refp's layout less level 0; NULL when L == 1), kept for backward. */
+int dgv2_msml_fwd(float* loss, float* genp, const float* gen, const float* refp, const float* maskp, const float* normp,
+                  const float* invm, int B, int C, int H, int W, int L, int metric, int relative, void* stream);
+/* ggen [B,C,H,W] = gloss[b] * d loss[b] / d gen (sign(0) = 0 for l1).  gscratch: genp's size, the gradients of levels
+ * 1 .. L-1 on their way down.  replaces: autograd through gans/inversion.py:23-29,48-76. */
+int dgv2_msml_bwd(float* ggen, float* gscratch, const float* gloss, const float* gen, const float* genp,
+                  const float* refp, const float* maskp, const float* normp, const float* invm, int B, int C, int H, int W,
+                  int L, int metric, int relative, void* stream);
+/* Input gradient of dgv2_coords_convert (same modes, same in / mask / angle): gx [B,1,H,W] from gout ([B,1,H,W], modes
+ * 2 / 3: [B,3,H,W]).  The validity masks are constants, d(1/(x+tol)) = -1/(x+tol)^2, mode 0 with a mask carries the
+ * factor 2 mask of its blend.  replaces: autograd through CoordBridge.convert, gans/coords.py:88-185
+ *   (demo_inversion.py:169 differentiates inv_depth_norm -> depth_norm). */
+int dgv2_coords_convert_bwd(float* gx, const float* gout, const float* in, const float* mask, const float* angle, int B,
+                            int H, int W, float min_depth, float max_depth, int mode, void* stream);
+/* Angle gradient of dgv2_fourier_feature: g [B,H,W,ld] (dtype) holds the gradient of the encoding in channels
+ * [c0, c0+2F) -> g_angle fp32 [B,2,H,W], g_a = sum_f freqs[f,a] (g_sin[f] cos c_f - g_cos[f] sin c_f) with c_f
+ * recomputed from angle [Ba,2,H,W] (+ shift [B] on the azimuth).  replaces: autograd through the 1x1 conv + sin / cos
+ *   of gans/models/ops/fourier.py:77-82 (demo_inversion.py:164 optimises angle + phase). */
+int dgv2_fourier_feature_bwd(float* g_angle, const void* g, const float* angle, const float* shift, const float* freqs,
+                             const float* phase, int B, int Ba, int H, int W, int F, int ld, int c0, int dtype,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
