@@ -191,30 +191,21 @@ class Conv2d(nn.Sequential):
                 w = F.pad(w, (0, pad_in_to - w.shape[3]))
             if wscale is not None:
                 w = w * wscale
-        if fp8 is not None:   # e4m3 operands: x = (handle, payload); the bank's handle carries the bf16 backward operands
-            assert ent is not None and b is None and not fork and down is None
-            handle, x8 = x
-            if resid is not None:
-                assert act is None
-                return native.conv_ring_resid_fp8(handle, x8, w, fp8[0], fp8[1], resid, geom)
-            assert act is not None and act.bias is not None
-            return native.conv_ring_act_fp8(handle, x8, w, fp8[0], fp8[1], act.bias, geom, act.negative_slope,
-                                            act.scale if act_scale is None else act_scale)
-        if resid is not None:   # conv(x, w) + resid in one launch (bias-free, activation-free skip conv)
-            assert b is None and act is None
-            return native.conv_ring_resid(x, w if ent is not None else w.contiguous(), resid, geom)
-        if down is not None:   # conv + act + blur/down as one node (native._ConvActDown); -> y or (y, x) with fork
-            assert act is not None and b is None and act.bias is not None and resid is None and ent is not None
-            return native.conv_ring_act_down(x, w, act.bias, geom, down, act.negative_slope,
-                                             act.scale if act_scale is None else act_scale, fork=fork, q8=q8)
-        if fork:   # -> (activation, x handed on to the sibling branch); see native._ConvActFork
-            assert act is not None and b is None and act.bias is not None and resid is None
-            return native.conv_ring_act_fork(x, w if ent is not None else w.contiguous(), act.bias, geom,
-                                             act.negative_slope, act.scale if act_scale is None else act_scale)
-        if act is not None and b is None and act.bias is not None:
-            return native.conv_ring_act(x, w if ent is not None else w.contiguous(), act.bias, geom, act.negative_slope,
-                                        act.scale if act_scale is None else act_scale)
-        y = native.conv_ring(x, w if ent is not None else w.contiguous(), geom)
+        # bias + lrelu ride in the conv kernel's epilogue when the conv has no bias of its own; ONE node (native._Conv) then
+        # also takes the blur/down behind the activation, the fork of x to a sibling branch, the residual sum and the e4m3
+        # forms: -> y, (y, x) with fork, (handle, payload[, x]) with q8
+        fused = act is not None and b is None and act.bias is not None
+        assert resid is None or (b is None and act is None), "the residual sum is a bias-free, activation-free conv's"
+        assert ent is not None or (down is None and fp8 is None), "blur/down and e4m3 operands need the weight bank"
+        plain = not fork and down is None and fp8 is None
+        ep = native.ConvEpilogue(
+            geom, act=(float(act.negative_slope), float(act.scale if act_scale is None else act_scale)) if fused else None,
+            down=down, fork=bool(fork), q8=bool(q8), resid=resid is not None, fp8=fp8,
+            # the caller's promise (Discriminator.forward: the features of a bf16 trunk widened to fp32 for the epilogue)
+            x_exact=int(getattr(x, "_dgv2_exact", 0)) if fused and plain else 0)
+        y = native.conv_ring_ep(x, w if ent is not None else w.contiguous(), ep, act.bias if fused else None, resid)
+        if fused or resid is not None:
+            return y
         if b is not None:
             y = y + (b * gain).to(y.dtype)
         return y if act is None else act.forward_cl(y)

@@ -94,7 +94,7 @@ class _BiasActBackward(Function):
 class _BiasAct(Function):
     @staticmethod
     def forward(ctx, x, bias, alpha, scale, step_b):
-        ctx.set_materialize_grads(False)   # an absent cotangent stays absent (see conv._ConvAct)
+        ctx.set_materialize_grads(False)   # an absent cotangent stays absent (see conv._Conv)
         x = x.contiguous()
         size_b = 1 if bias is None else bias.numel()
         out = _bias_act_raw(x, None if bias is None else bias.contiguous(), None, 0, alpha, scale, step_b, size_b)

@@ -3,7 +3,6 @@
 Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring); the
 parts import each other in order, every name stays reachable as native.<name>.
 """
-import math
 import contextlib
 import os
 from typing import NamedTuple, Optional
@@ -63,18 +62,15 @@ def _conv_taps_ex(y, x, w3, Hg, Wg, in_stride, ioff, out_stride, classes, taps4,
     B, Hin, Win, Cin = x.shape
     O, wtaps, _ = w3.shape
     _, Hy, Wy, ldy = y.shape
+    carr = (_ct.c_int * (2 * len(classes)))(*[v for c in classes for v in c])
+    tarr = (_ct.c_int * (4 * len(taps4)))(*[v for t in taps4 for v in t])
+    earr = (_ct.c_int * max(5 * len(extras), 1))(*[v for e in extras for v in e])
     if ch0 is not None:
-        carr = (_ct.c_int * (2 * len(classes)))(*[v for c in classes for v in c])
-        tarr = (_ct.c_int * (4 * len(taps4)))(*[v for t in taps4 for v in t])
-        earr = (_ct.c_int * max(5 * len(extras), 1))(*[v for e in extras for v in e])
         es = y.element_size()
         rp = None if resid is None else resid.data_ptr() + ch0 * es
         return N.try_call("dgv2_conv_taps_ld", y.data_ptr() + ch0 * es, ldy, N.ptr(x), N.ptr(w3), B, Hin, Win, Cin, Hg, Wg,
                           O, Hy, Wy, in_stride, ioff[0], ioff[1], out_stride, len(classes), carr, len(taps4), wtaps,
                           tarr, len(extras), earr, int(hzero), 1, 0, None, rp, 0, 0.2, 1.0, _dt(x), N.stream())
-    carr = (_ct.c_int * (2 * len(classes)))(*[v for c in classes for v in c])
-    tarr = (_ct.c_int * (4 * len(taps4)))(*[v for t in taps4 for v in t])
-    earr = (_ct.c_int * max(5 * len(extras), 1))(*[v for e in extras for v in e])
     return N.try_call("dgv2_conv_taps_ex", N.ptr(y), N.ptr(x), N.ptr(w3), B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy,
                       in_stride, ioff[0], ioff[1], out_stride, len(classes), carr, len(taps4), wtaps, tarr,
                       len(extras), earr, int(hzero), 1, 0, None, N.ptr(resid), 0, 0.2, 1.0, _dt(x), N.stream())
@@ -400,51 +396,37 @@ class PreparedConv(NamedTuple):
     w8t: Optional[torch.Tensor] = None
 
 
-def _weights(ctx, w, x):
-    """What every conv Function's forward starts with: -> (weights in x's dtype [O,kh,kw,C], the forward staging image
-    or None) for _conv_fwd_raw, and ctx.bank = (wt, w8t, gscale) for _conv_grads.  A weight handle carries ONE attribute,
-    _dgv2_bank = (PreparedConv, gscale: see _ConvDgrad), put there by Conv2d.forward_cl / scaled_handle: the weights come
-    from its record when that was prepared in x's dtype, else from the tensor's own values (a handle has none: _values
-    raises)."""
+class ConvEpilogue(NamedTuple):
+    """What one _Conv node does around its conv (Conv2d.forward_cl builds it); the tensors that take gradients -- x, w, bias,
+    the residual -- are the node's own inputs.  Defaults: the bare conv."""
+    geom: ConvGeom
+    act: Optional[tuple] = None    # (alpha, scale): lrelu(conv + bias) * scale in the conv's epilogue
+    down: Optional[ResampleSpec] = None   # blur / decimation of the activation in the same node (needs act)
+    fork: bool = False             # also return x, for a sibling branch: its gradient joins in the data-gradient kernel
+    q8: bool = False               # (with down) the result leaves as e4m3: (bf16 handle, payload), see native.fp8
+    x_exact: int = 0               # channels [0, x_exact) of x hold bf16-representable values (conv_x3.hip)
+    resid: bool = False            # a residual is added in the conv's epilogue
+    fp8: Optional[tuple] = None    # (w8, descale) of native.fp8_quant_weights: x arrives as e4m3, contracted as e4m3
+
+    @property
+    def first_order(self):
+        """The fork / down / e4m3 forms were written for first-order passes behind the weight bank: they ask
+        ctx.needs_input_grad for the weight gradient and always produce the bias gradient, where the other forms ask
+        want_param_grad (off inside input_grads_only(): R1's first pass)."""
+        return self.fork or self.down is not None or self.fp8 is not None
+
+
+def _weights(ctx, w, dtype):
+    """What the conv node's forward starts with: -> (weights in `dtype` [O,kh,kw,C], the forward staging image or None) for
+    _conv_fwd_raw, and ctx.bank = (wt, w8t, gscale) for its backward.  A weight handle carries ONE attribute, _dgv2_bank =
+    (PreparedConv, gscale: see _ConvDgrad), put there by Conv2d.forward_cl / scaled_handle: the weights come from its
+    record when that was prepared in `dtype`, else from the tensor's own values (a handle has none: _values raises)."""
     rec, gscale = getattr(w, "_dgv2_bank", (None, None))
-    if rec is None or rec.wf.dtype != x.dtype:
+    if rec is None or rec.wf.dtype != dtype:
         ctx.bank = (None, None, gscale)
-        return _values(w, x.dtype).reshape(w.shape), None
+        return _values(w, dtype).reshape(w.shape), None
     ctx.bank = (rec.wt, rec.w8t, gscale)
     return rec.wf.reshape(w.shape), rec.w8   # (an fp32 record's images are conv_x3.hip's bf16 planes)
-
-
-def _conv_grads(ctx, gy, x, w, g, want_gw, resid=None, xexact=0):
-    """(gx [+ resid], gw) of a conv Function whose forward ran _weights; each is None where it is not asked for
-    (want_gw: the class's own guard for the weight gradient)."""
-    wt, w8t, gscale = ctx.bank
-    gx = _dgrad(gy, w, g, tuple(x.shape), wt, resid, gscale, w8t) if ctx.needs_input_grad[0] else None
-    if not want_gw:
-        return gx, None
-    # the conv ran on conv_x3.hip's plane images (fp32 behind the weight bank): its weight gradient does too; x3 = the
-    # conv's input channel count before padding
-    x3 = None
-    if gy.dtype == torch.float32 and w8t is not None and w8t.dtype == torch.bfloat16:
-        x3 = getattr(w8t, "_dgv2_clive", None)
-    return gx, _ConvWgrad.apply(gy, x, g, gscale, x3, xexact, _wgrad_out(w, gscale))
-
-
-class _ConvFwd(Function):
-    @staticmethod
-    def forward(ctx, x, w, g):
-        ctx.set_materialize_grads(False)   # an absent cotangent stays absent (see _ConvAct)
-        x = x.contiguous()
-        wc, w8 = _weights(ctx, w, x)
-        ctx.save_for_backward(x, w)
-        ctx.g = g
-        return _conv_fwd_raw(x, wc, g, w8=w8)
-
-    @staticmethod
-    def backward(ctx, gy):
-        if gy is None:
-            return None, None, None
-        x, w = ctx.saved_tensors
-        return _conv_grads(ctx, gy, x, w, ctx.g, want_param_grad(ctx, 1)) + (None,)
 
 
 def _dgrad(gy, w, g, xshape, wt=None, resid=None, gscale=None, w8t=None):
@@ -472,7 +454,7 @@ class _ConvDgrad(Function):
     @staticmethod
     def backward(ctx, ggx):
         gy, w = ctx.saved_tensors
-        g_gy = _ConvFwd.apply(ggx, w, ctx.g) if ctx.needs_input_grad[0] else None
+        g_gy = conv_ring(ggx, w, ctx.g) if ctx.needs_input_grad[0] else None
         g_w = _ConvWgrad.apply(gy, ggx, ctx.g, ctx.gscale) if ctx.needs_input_grad[1] else None
         return g_gy, g_w, None, None, None, (ggx if ctx.needs_input_grad[5] else None), None, None
 
@@ -505,46 +487,9 @@ class _ConvWgrad(Function):
         if ctx.gscale is not None:   # out = gscale * wgrad(gy, x)
             ggw = ggw * ctx.gscale
         gy, x = ctx.saved_tensors
-        g_gy = _ConvFwd.apply(x, ggw, ctx.g) if ctx.needs_input_grad[0] else None
+        g_gy = conv_ring(x, ggw, ctx.g) if ctx.needs_input_grad[0] else None
         g_x = _dgrad(gy, ggw, ctx.g, tuple(x.shape)) if ctx.needs_input_grad[1] else None
         return g_gy, g_x, None, None, None, None, None
-
-
-def conv_ring(x, w, geom):
-    """x [B,H,W,C]; w fp32 master in channels-last filter layout [O,kh,kw,C]."""
-    return _ConvFwd.apply(x, w, geom)
-
-
-class _ConvAct(Function):
-    """lrelu(conv(x, w) + b) * scale, bias/activation fused into the conv epilogue; the backward is
-    composed of differentiable Functions so R1's double backward stays on the HIP kernels."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, g, alpha, scale):
-        # The second pass of R1 reaches this node's OUTPUT through the activation backward of the first pass (which
-        # saved it) with NO gradient (the leaky ReLU's mask has none): with materialised grads the engine would run the
-        # whole backward below on a zero tensor -- for the fp32 epilogue conv a data and a weight gradient of zeros,
-        # 0.9 ms per R1 iteration.
-        ctx.set_materialize_grads(False)
-        # the caller's promise (Discriminator.forward: the features of a bf16 trunk widened to fp32 for the epilogue):
-        # channels [0, n) of x are bf16-representable -- conv_x3.hip skips their zero planes (forward, weight gradient)
-        ctx.x_exact = int(getattr(x, "_dgv2_exact", 0))
-        x = x.contiguous()
-        wc, w8 = _weights(ctx, w, x)
-        out = _conv_fwd_raw(x, wc, g, bias.detach().float().contiguous(), 3, alpha, scale, w8=w8, xexact=ctx.x_exact)
-        ctx.save_for_backward(x, w, out)
-        ctx.cfg = (g, alpha, scale, bias.numel())
-        return out
-
-    @staticmethod
-    def backward(ctx, gy):
-        if gy is None:
-            return (None,) * 6
-        x, w, out = ctx.saved_tensors
-        g, alpha, scale, size_b = ctx.cfg
-        gpre, gb = _BiasActBackward.apply(gy, out, want_param_grad(ctx, 2), alpha, scale, 1, size_b)
-        gx, gw = _conv_grads(ctx, gpre, x, w, g, want_param_grad(ctx, 1), xexact=ctx.x_exact)
-        return gx, gw, gb, None, None, None
 
 
 class _LinearLow(Function):
@@ -988,36 +933,6 @@ def conv_weight_bank(entries, dtype, image8=None):
     return list(zip(wfs, wts, w8s, w8ts))
 
 
-class _ConvActFork(Function):
-    """(lrelu(conv(x, w) + b) * scale, x): the second output hands the SAME input on to a sibling branch (the skip
-    path of ResidualBlock), so that in backward both gradients of x arrive here together and the sibling's is added
-    in the epilogue of this conv's data-gradient kernel -- no separate fork-point add over the activation."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, g, alpha, scale):
-        ctx.set_materialize_grads(False)
-        x = x.contiguous()
-        wc, w8 = _weights(ctx, w, x)
-        out = _conv_fwd_raw(x, wc, g, bias.detach().float().contiguous(), 3, alpha, scale, w8=w8)
-        ctx.save_for_backward(x, w, out)
-        ctx.cfg = (g, alpha, scale, bias.numel())
-        return out, x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, gy, gx_sibling):
-        x, w, out = ctx.saved_tensors
-        g, alpha, scale, size_b = ctx.cfg
-        if gy is None:   # only the sibling branch carries a gradient
-            return gx_sibling, None, None, None, None, None
-        gpre, gb = _BiasActBackward.apply(gy, out, True, alpha, scale, 1, size_b)
-        gx, gw = _conv_grads(ctx, gpre, x, w, g, ctx.needs_input_grad[1], resid=gx_sibling)
-        return gx, gw, gb, None, None, None
-
-
-def conv_ring_act_fork(x, w, bias, geom, alpha=0.2, scale=math.sqrt(2.0)):
-    return _ConvActFork.apply(x, w, bias, geom, float(alpha), float(scale))
-
-
 _ACTBWD_BLOCKS = {}
 
 
@@ -1059,88 +974,115 @@ def _resample_actbwd(g, out, spec, in_hw, alpha, scale):
     return gpre, gb
 
 
-class _ConvActDown(Function):
-    """resample(lrelu(conv(x, w) + b) * scale) [, x]: conv1 -> FusedLeakyReLU -> blur/down of ResidualBlock
-    (dusty_v2.py:325-345) as one autograd node, so that the backward can run the adjoint resampling and the
-    activation backward (+ bias gradient) in ONE pass over the full-resolution gradient instead of two, and (fork)
-    add the skip branch's gradient of x in the data-gradient epilogue.  First-order passes with the weight bank."""
+class _Conv(Function):
+    """The discriminator's ring-padded conv with everything ConvEpilogue describes, as ONE autograd node:
+    [resample](lrelu(conv(x, w) + b) * scale) or conv(x, w) + resid or conv(x, w) [, x for a sibling branch].  The bias /
+    activation / residual ride in the conv kernel's epilogue; with `down` the backward runs the adjoint resampling and the
+    activation backward (+ bias gradient) in one pass over the full-resolution gradient; with `fork` both gradients of x
+    arrive here together and the sibling's is added in the epilogue of the data-gradient kernel.  The backward is composed
+    of differentiable Functions ({_Conv, _ConvDgrad, _ConvWgrad} call each other), so R1's double backward stays on the
+    HIP kernels.  ep.fp8: x is the bf16 handle, x8 its e4m3 payload; the gradients are bf16, the weight gradient against
+    the dequantised payload."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, g, alpha, scale, spec, fork, q8=False):
-        """q8: the blurred activation leaves as e4m3 (native.fp8): -> (bf16 handle carrying the autograd edge, e4m3
-        payload[, x])."""
+    def forward(ctx, x, w, bias, resid, x8, ep):
+        # An absent cotangent stays absent.  The second pass of R1 reaches an activation node's OUTPUT through the activation
+        # backward of the first pass (which saved it) with NO gradient (the leaky ReLU's mask has none): with materialised
+        # grads the engine would run the whole backward below on a zero tensor -- for the fp32 epilogue conv a data and a
+        # weight gradient of zeros, 0.9 ms per R1 iteration.
         ctx.set_materialize_grads(False)
-        x = x.contiguous()
-        wc, w8 = _weights(ctx, w, x)
-        out = _conv_fwd_raw(x, wc, g, bias.detach().float().contiguous(), 3, alpha, scale, w8=w8)
-        in_hw = (out.shape[1], out.shape[2])
-        ctx.save_for_backward(x, w, out)
-        ctx.cfg = (g, alpha, scale, bias.numel(), spec, in_hw)
-        ctx.q8 = bool(q8)
-        if q8:
+        assert (ep.act is not None) == (bias is not None) and ep.resid == (resid is not None) and not (ep.act and ep.resid)
+        assert ep.act is not None or (ep.down is None and not ep.fork), "blur/down and fork belong to the activation's forms"
+        assert ep.fp8 is None or (ep.down is None and not ep.fork), "an e4m3 input has no blur/down or fork form"
+        alpha, scale = ep.act or (0.2, 1.0)
+        act = 0 if ep.act is None else 3
+        if bias is not None:
+            ctx.size_b = bias.numel()
+            bias = bias.detach().float().contiguous()
+        if resid is not None:
+            resid = resid.contiguous()
+        if ep.fp8 is not None:
+            from .fp8 import _conv_fwd_fp8
+            _weights(ctx, w, torch.bfloat16)   # the handle's record carries the bf16 operands of the backward
+            x = x8
+            out = _conv_fwd_fp8(x8, ep.fp8[0], ep.fp8[1], ep.geom, bias, act, alpha, scale, resid)
+        else:
+            x = x.contiguous()
+            wc, w8 = _weights(ctx, w, x.dtype)
+            out = _conv_fwd_raw(x, wc, ep.geom, bias, act, alpha, scale, resid, w8, ep.x_exact)
+        ctx.save_for_backward(x, w, *(() if ep.act is None else (out,)))
+        ctx.ep = ep
+        if ep.down is None:
+            y = (out,)
+        elif ep.q8:
             from .fp8 import _handle, _resample_q8_raw
-            y8 = _resample_q8_raw(out, spec, in_hw)
+            y8 = _resample_q8_raw(out, ep.down, tuple(out.shape[1:3]))
             if y8 is None:
                 raise RuntimeError("dgv2: no e4m3 resampling kernel covers this shape (check native.fp8_ok first)")
             ctx.mark_non_differentiable(y8)
-            return (_handle(y8.shape, x.device), y8) + ((x.view_as(x),) if fork else ())
-        y = _resample_raw(out, spec, False, in_hw)
-        return (y, x.view_as(x)) if fork else y
+            y = (_handle(y8.shape, x.device), y8)
+        else:
+            y = (_resample_raw(out, ep.down, False, tuple(out.shape[1:3])),)
+        if ep.fork:
+            y += (x.view_as(x),)
+        return y if len(y) > 1 else y[0]
 
     @staticmethod
     def backward(ctx, gy, *rest):
-        x, w, out = ctx.saved_tensors
-        g, alpha, scale, size_b, spec, in_hw = ctx.cfg
-        rest = rest[1:] if ctx.q8 else rest          # q8: rest[0] is the (absent) gradient of the e4m3 payload
-        gx_sibling = rest[0] if rest else None
-        if gy is None:
-            return gx_sibling, None, None, None, None, None, None, None, None
-        fused = None if torch.is_grad_enabled() else _resample_actbwd(gy.to(out.dtype), out, spec, in_hw, alpha, scale)
-        if fused is not None:
-            gpre, gb = fused
-        else:   # composed (also the differentiable form for create_graph=True)
-            gh = _Resample.apply(gy, spec, True, in_hw)
-            gpre, gb = _BiasActBackward.apply(gh, out, True, alpha, scale, 1, size_b)
-        gx, gw = _conv_grads(ctx, gpre, x, w, g, ctx.needs_input_grad[1], resid=gx_sibling)
-        return (gx if ctx.needs_input_grad[0] else gx_sibling), gw, gb, None, None, None, None, None, None
+        ep = ctx.ep
+        gx_sibling = rest[-1] if ep.fork else None   # (q8: rest[0] is the absent gradient of the e4m3 payload)
+        if gy is None:   # at most the sibling branch carries a gradient
+            return gx_sibling, None, None, None, None, None
+        x, w, *out = ctx.saved_tensors
+        want_gw = ctx.needs_input_grad[1] if ep.first_order else want_param_grad(ctx, 1)
+        gb = None
+        if ep.act is not None:
+            out, (alpha, scale) = out[0], ep.act
+            fused = None
+            if ep.down is not None:
+                in_hw = tuple(out.shape[1:3])
+                if not torch.is_grad_enabled():
+                    fused = _resample_actbwd(gy.to(out.dtype), out, ep.down, in_hw, alpha, scale)
+                if fused is None:   # composed (also the differentiable form for create_graph=True)
+                    gy = _Resample.apply(gy, ep.down, True, in_hw)
+            want_gb = ep.first_order or want_param_grad(ctx, 2)
+            gy, gb = fused or _BiasActBackward.apply(gy, out, want_gb, alpha, scale, 1, ctx.size_b)
+        wt, w8t, gscale = ctx.bank
+        gx, gw = gx_sibling, None
+        if ep.fp8 is not None:   # bf16 gradients on the direct engine (no w8t), against the dequantised payload
+            from .fp8 import fp8_dequant
+            if ep.resid:
+                gy = gy.contiguous()
+            if ctx.needs_input_grad[0]:
+                gx = _dgrad(gy, w, ep.geom, tuple(x.shape), wt, None, gscale)
+            if want_gw:
+                gw = _ConvWgrad.apply(gy, fp8_dequant(x), ep.geom, gscale)
+        else:
+            if ctx.needs_input_grad[0]:
+                gx = _dgrad(gy, w, ep.geom, tuple(x.shape), wt, gx_sibling, gscale, w8t)
+            if want_gw:
+                # the conv ran on conv_x3.hip's plane images (fp32 behind the weight bank): its weight gradient does too;
+                # x3 = the conv's input channel count before padding
+                x3 = None
+                if gy.dtype == torch.float32 and w8t is not None and w8t.dtype == torch.bfloat16:
+                    x3 = getattr(w8t, "_dgv2_clive", None)
+                gw = _ConvWgrad.apply(gy, x, ep.geom, gscale, x3, ep.x_exact, _wgrad_out(w, gscale))
+        return gx, gw, gb, (gy if ep.resid and ctx.needs_input_grad[3] else None), None, None
 
 
-def conv_ring_act_down(x, w, bias, geom, spec, alpha=0.2, scale=math.sqrt(2.0), fork=False, q8=False):
-    return _ConvActDown.apply(x, w, bias, geom, float(alpha), float(scale), spec, bool(fork), bool(q8))
+def conv_ring_ep(x, w, ep, bias=None, resid=None):
+    """The conv `ep` (a ConvEpilogue) describes; x is (bf16 handle, e4m3 payload) when ep.fp8 is set.  -> y, (y, x) with
+    ep.fork, (handle, payload[, x]) with ep.q8."""
+    x, x8 = x if ep.fp8 is not None else (x, None)
+    return _Conv.apply(x, w, bias, resid, x8, ep)
 
 
-class _ConvResid(Function):
-    """conv(x, w) + resid with the residual added in the conv epilogue (reference: the skip sum of
-    ResidualBlock.forward, dusty_v2.py:343-345)."""
-
-    @staticmethod
-    def forward(ctx, x, w, resid, g):
-        ctx.set_materialize_grads(False)
-        x = x.contiguous()
-        resid = resid.contiguous()
-        wc, w8 = _weights(ctx, w, x)
-        ctx.save_for_backward(x, w)
-        ctx.g = g
-        return _conv_fwd_raw(x, wc, g, resid=resid, w8=w8)
-
-    @staticmethod
-    def backward(ctx, gy):
-        if gy is None:
-            return None, None, None, None
-        x, w = ctx.saved_tensors
-        gx, gw = _conv_grads(ctx, gy, x, w, ctx.g, want_param_grad(ctx, 1))
-        return gx, gw, (gy if ctx.needs_input_grad[2] else None), None
-
-
-def conv_ring_resid(x, w, resid, geom):
-    return _ConvResid.apply(x, w, resid, geom)
+def conv_ring(x, w, geom):
+    """x [B,H,W,C]; w fp32 master in channels-last filter layout [O,kh,kw,C]."""
+    return conv_ring_ep(x, w, ConvEpilogue(geom))
 
 
 def conv_resid_ok(x, geom):
     return _direct_ok(geom, x.shape[3] % _kstep(x) == 0)
-
-
-def conv_ring_act(x, w, bias, geom, alpha=0.2, scale=math.sqrt(2.0)):
-    return _ConvAct.apply(x, w, bias, geom, float(alpha), float(scale))
 
 __all__ = [n_ for n_ in dir() if not n_.startswith("__")]

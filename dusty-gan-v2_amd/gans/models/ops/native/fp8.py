@@ -4,7 +4,6 @@ Part of gans.models.ops.native.  An e4m3 tensor never crosses an autograd edge (
 e4m3): the producers return a zero-storage bf16 HANDLE of the tensor's shape, which carries the edge, next to the e4m3
 payload (non-differentiable); the consumers take both.  First-order passes only -- R1's double backward runs the bf16
 ops (reference: the fp16 autocast switch of gans/models/dusty_v2.py:388-394)."""
-import math
 
 import torch
 from torch.autograd import Function
@@ -109,64 +108,6 @@ def _conv_fwd_fp8(x8, w8, descale, g, bias=None, act=0, alpha=0.2, scale=1.0, re
     N.call("dgv2_conv_taps_fp8", N.ptr(y), N.ptr(x8), N.ptr(w8), N.ptr(descale), B, H, W, C, Ho, Wo, O, Ho, Wo, g.stride, 0,
            0, len(taps), g.kh * g.kw, arr, 1, N.ptr(bias), N.ptr(resid), act, alpha, scale, N.stream())
     return y
-
-
-class _ConvAct8(Function):
-    """lrelu(conv(x8, w8) * descale + b) * scale on e4m3 operands (the forward of _ConvAct); backward in bf16: data
-    gradient from the bank's transposed bf16 weights, weight gradient against the dequantised saved activations."""
-
-    @staticmethod
-    def forward(ctx, handle, x8, w, w8, descale, bias, g, alpha, scale):
-        ctx.set_materialize_grads(False)
-        out = _conv_fwd_fp8(x8, w8, descale, g, bias.detach().float().contiguous(), 3, alpha, scale)
-        rec, ctx.gscale = getattr(w, "_dgv2_bank", (None, None))   # conv._weights: the handle's one attribute
-        ctx.wt = None if rec is None else rec.wt
-        ctx.save_for_backward(x8, w, out)
-        ctx.cfg = (g, alpha, scale, bias.numel())
-        return out
-
-    @staticmethod
-    def backward(ctx, gy):
-        if gy is None:
-            return (None,) * 9
-        x8, w, out = ctx.saved_tensors
-        g, alpha, scale, size_b = ctx.cfg
-        gpre, gb = _BiasActBackward.apply(gy, out, True, alpha, scale, 1, size_b)
-        gx = _dgrad(gpre, w, g, tuple(x8.shape), ctx.wt, None, ctx.gscale) if ctx.needs_input_grad[0] else None
-        gw = _ConvWgrad.apply(gpre, fp8_dequant(x8), g, ctx.gscale) if ctx.needs_input_grad[2] else None
-        return gx, None, gw, None, None, gb, None, None, None
-
-
-class _ConvResid8(Function):
-    """conv(x8, w8) * descale + resid on e4m3 operands (the forward of _ConvResid)."""
-
-    @staticmethod
-    def forward(ctx, handle, x8, w, w8, descale, resid, g):
-        ctx.set_materialize_grads(False)
-        resid = resid.contiguous()
-        rec, ctx.gscale = getattr(w, "_dgv2_bank", (None, None))   # conv._weights: the handle's one attribute
-        ctx.wt = None if rec is None else rec.wt
-        ctx.save_for_backward(x8, w)
-        ctx.g = g
-        return _conv_fwd_fp8(x8, w8, descale, g, resid=resid)
-
-    @staticmethod
-    def backward(ctx, gy):
-        if gy is None:
-            return (None,) * 7
-        x8, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = _dgrad(gy, w, ctx.g, tuple(x8.shape), ctx.wt, None, ctx.gscale) if ctx.needs_input_grad[0] else None
-        gw = _ConvWgrad.apply(gy, fp8_dequant(x8), ctx.g, ctx.gscale) if ctx.needs_input_grad[2] else None
-        return gx, None, gw, None, None, (gy if ctx.needs_input_grad[5] else None), None
-
-
-def conv_ring_act_fp8(handle, x8, w, w8, descale, bias, geom, alpha=0.2, scale=math.sqrt(2.0)):
-    return _ConvAct8.apply(handle, x8, w, w8, descale, bias, geom, float(alpha), float(scale))
-
-
-def conv_ring_resid_fp8(handle, x8, w, w8, descale, resid, geom):
-    return _ConvResid8.apply(handle, x8, w, w8, descale, resid, geom)
 
 
 import ctypes as _ct
