@@ -49,19 +49,30 @@ __global__ void upfirdn2d_kernel(T* __restrict__ out, const T* __restrict__ in, 
 
 constexpr int ADA_TW = 64;  // output columns per block
 
+// cutout (adaptive_augment.py:607-621): pixel (i, j) survives when its centre is at least half the box size away from the box
+// centre along x OR along y.  cut4 = (centre x, centre y, size x, size y) in units of the image; the distance is the
+// reference's plain abs(), NOT a ring distance, and a size of 0 keeps everything (|d| >= 0).
+__device__ __forceinline__ bool ada_cut_keep(const float* __restrict__ cut4, int i, int j, int H, int W) {
+  const float dx = fabsf(((float)j + 0.5f) / (float)W - cut4[0]);
+  const float dy = fabsf(((float)i + 0.5f) / (float)H - cut4[1]);
+  return dx >= cut4[2] * 0.5f || dy >= cut4[3] * 0.5f;
+}
+
 // Generic version: any H (dynamic LDS = H * ADA_TW floats).  Kept for H > 64 or H % 4 != 0.
 __global__ __launch_bounds__(256) void ada_apply_kernel(float* __restrict__ y, const float* __restrict__ x,
                                                         const float* __restrict__ Ay, const float* __restrict__ kx,
                                                         const int* __restrict__ off, const int* __restrict__ sgn,
                                                         const float* __restrict__ a, const float* __restrict__ c,
-                                                        int H, int W, int K, int transpose) {
+                                                        const float* __restrict__ cut, const float* __restrict__ sigma,
+                                                        const float* __restrict__ eps, int H, int W, int K, int transpose) {
   extern __shared__ float tmp[];  // [H][ADA_TW] horizontally filtered tile
   const int b = blockIdx.y;
   const int j0 = blockIdx.x * ADA_TW;
   const float* xb = x + (int64_t)b * H * W;
   const float* kb = kx + (int64_t)b * K;
   const int of = off[b], sg = sgn[b];
-  // phase 1: t[h][j] = sum_t kx[t] * x[h][col(j, t)]
+  const float* cb4 = cut ? cut + (int64_t)b * 4 : nullptr;
+  // phase 1: t[h][j] = sum_t kx[t] * x[h][col(j, t)]   (the adjoint reads the cotangent through the cutout mask)
   for (int it = threadIdx.x; it < H * ADA_TW; it += blockDim.x) {
     const int jl = it % ADA_TW, h = it / ADA_TW;
     const int j = j0 + jl;
@@ -69,7 +80,9 @@ __global__ __launch_bounds__(256) void ada_apply_kernel(float* __restrict__ y, c
     if (j < W) {
       for (int t = 0; t < K; ++t) {
         const int col = transpose ? floormod(sg * (j - of - t), W) : floormod(sg * j + of + t, W);
-        acc += kb[t] * xb[(int64_t)h * W + col];
+        float xv = xb[(int64_t)h * W + col];
+        if (transpose && cb4 && !ada_cut_keep(cb4, h, col, H, W)) xv = 0.f;
+        acc += kb[t] * xv;
       }
     }
     tmp[it] = acc;
@@ -79,13 +92,19 @@ __global__ __launch_bounds__(256) void ada_apply_kernel(float* __restrict__ y, c
   const float* Ab = Ay + (int64_t)b * H * H;
   const float ab = a[b];
   const float cb = (transpose || !c) ? 0.f : c[b];
+  const bool noisy = !transpose && sigma && eps;
+  const float sb = noisy ? sigma[b] : 0.f;
   for (int it = threadIdx.x; it < H * ADA_TW; it += blockDim.x) {
     const int jl = it % ADA_TW, i = it / ADA_TW;
     const int j = j0 + jl;
     if (j >= W) continue;
     float acc = 0.f;
     for (int h = 0; h < H; ++h) acc += (transpose ? Ab[h * H + i] : Ab[i * H + h]) * tmp[h * ADA_TW + jl];
-    y[((int64_t)b * H + i) * W + j] = ab * acc + cb;
+    const int64_t o = ((int64_t)b * H + i) * W + j;
+    float v = ab * acc + cb;
+    if (noisy) v = fmaf(sb, eps[o], v);
+    if (!transpose && cb4 && !ada_cut_keep(cb4, i, j, H, W)) v = 0.f;
+    y[o] = v;
   }
 }
 
@@ -185,6 +204,135 @@ __global__ __launch_bounds__(256) void ada_apply_lds_kernel(float* __restrict__ 
   }
 }
 
+// Image-space form of the LDS kernel (adaptive_augment.py:547-621 folded in, see dgv2_ada_fold): the taps are the composite of
+// the geometric x-filter and the 43-tap band filter, K' = K + 42 = 74 today, plus the cutout mask and the additive noise in
+// the staging / the epilogue.  The K <= 64 kernel above holds xt, tmp and the operator side by side in 62 KB; with
+// ADA_TW + K' - 1 = 137 staged columns that layout needs 69 KB.  The operator is only read in phase 2 and the source tile
+// only in phase 1, so here the operator is fetched into registers before phase 1 (16 floats per thread, its global latency
+// hidden behind the taps) and written over the source tile once phase 1 is done: 53.8 KB static, three blocks per CU
+// instead of two.  The row pitch 145 = 1 (mod 4) keeps the two rows a 32-lane half reads in phase 1 on different banks.
+constexpr int ADA2_KMAX = 80;
+constexpr int ADA2_XT = 145;   // >= ADA_TW + ADA2_KMAX - 1 staged source columns
+static_assert(ADA2_XT >= ADA_TW + ADA2_KMAX - 1, "source tile pitch");
+static_assert(ADA_HMAX * ADA2_XT >= ADA_HMAX * ADA_HMAX, "the operator overlays the source tile");
+
+__global__ __launch_bounds__(256) void ada_apply_img_lds_kernel(float* __restrict__ y, const float* __restrict__ x,
+                                                                const float* __restrict__ Ay, const float* __restrict__ kx,
+                                                                const int* __restrict__ off, const int* __restrict__ sgn,
+                                                                const float* __restrict__ a, const float* __restrict__ c,
+                                                                const float* __restrict__ cut, const float* __restrict__ sigma,
+                                                                const float* __restrict__ eps, int H, int W, int K,
+                                                                int transpose) {
+  __shared__ __attribute__((aligned(16))) float xt[ADA_HMAX * ADA2_XT];   // phase 1: xt[h][q]; phase 2: Al[i][h]
+  __shared__ float tmp[ADA_HMAX][ADA_TW];
+  __shared__ float kl[ADA2_KMAX];
+  float (*Al)[ADA_HMAX] = reinterpret_cast<float (*)[ADA_HMAX]>(xt);
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int j0 = blockIdx.x * ADA_TW;
+  const float* xb = x + (int64_t)b * H * W;
+  const float* Ab = Ay + (int64_t)b * H * H;
+  const int of = off[b], sg = sgn[b];
+  float c4[4] = {0.f, 0.f, 0.f, 0.f};
+  if (cut) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c4[k] = cut[(int64_t)b * 4 + k];
+  }
+  // the operator, into registers now and into LDS after phase 1
+  float av[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const int it = tid + 256 * k;
+    av[k] = it < H * H ? Ab[it] : 0.f;
+  }
+  // source column of (jl, t) as in ada_apply_lds_kernel: c0 + qa*jl + qb*t, LDS column q = qa*jl + qb*t + qs >= 0
+  const int qa = sg, qb = transpose ? -sg : 1;
+  const int c0 = transpose ? sg * (j0 - of) : sg * j0 + of;
+  const int qs = (qa < 0 ? ADA_TW - 1 : 0) + (qb < 0 ? K - 1 : 0);
+  const int nq = ADA_TW + K - 1;   // <= 143
+  // staging: an item is one source column (one wrap computation) times a quarter of the rows; the adjoint reads the
+  // cotangent through the cutout mask
+  {
+    const int rq = H / 4;
+    const bool masked = transpose && cut;
+    for (int it = tid; it < 4 * nq; it += 256) {
+      const int part = it / nq, q = it - part * nq;
+      const int col = floormod(c0 + q - qs, W);
+      const float* src = xb + col;
+#pragma unroll 4
+      for (int h = part * rq; h < (part + 1) * rq; ++h) {
+        float v = src[(int64_t)h * W];
+        if (masked && !ada_cut_keep(c4, h, col, H, W)) v = 0.f;
+        xt[h * ADA2_XT + q] = v;
+      }
+    }
+  }
+  if (tid < K) kl[tid] = kx[(int64_t)b * K + tid];
+  __syncthreads();
+  // phase 1: the sliding window of ada_apply_lds_kernel (four consecutive outputs per item, two LDS reads per four FMAs)
+  for (int it = tid; it < H * (ADA_TW / 4); it += 256) {
+    const int jg = it % (ADA_TW / 4), h = it / (ADA_TW / 4);
+    const int pb = (qa > 0 ? 4 * jg : -4 * jg - 3) + qs + (qb > 0 ? 0 : -(K - 1));
+    const float* xr = &xt[h * ADA2_XT + pb];
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, k0 = 0.f, k1 = 0.f, k2 = 0.f, k3 = 0.f;
+    for (int u = 0; u < K + 3; ++u) {
+      const float xv = xr[u];
+      k3 = k2; k2 = k1; k1 = k0;
+      k0 = u < K ? kl[qb > 0 ? u : K - 1 - u] : 0.f;
+      a0 = fmaf(k0, xv, a0);
+      a1 = fmaf(k1, xv, a1);
+      a2 = fmaf(k2, xv, a2);
+      a3 = fmaf(k3, xv, a3);
+    }
+    float* tr = &tmp[h][4 * jg];
+    if (qa > 0) { tr[0] = a0; tr[1] = a1; tr[2] = a2; tr[3] = a3; }
+    else { tr[0] = a3; tr[1] = a2; tr[2] = a1; tr[3] = a0; }
+  }
+  __syncthreads();   // tmp complete, the source tile dead: the operator takes its place (transposed here for the adjoint)
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const int it = tid + 256 * k;
+    if (it < H * H) {
+      const int r = it / H, cidx = it - r * H;
+      if (transpose) Al[cidx][r] = av[k];
+      else Al[r][cidx] = av[k];
+    }
+  }
+  __syncthreads();
+  const int jl = tid % ADA_TW, ig = tid / ADA_TW;   // 4 row groups x 64 columns
+  const int rpt = H / 4;                             // output rows per thread (<= 16)
+  const int j = j0 + jl;
+  float acc[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int h = 0; h < H; h += 4) {
+    const float t0 = tmp[h][jl], t1 = tmp[h + 1][jl], t2 = tmp[h + 2][jl], t3 = tmp[h + 3][jl];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (r < rpt) {
+        const float4 w4 = *reinterpret_cast<const float4*>(&Al[ig * rpt + r][h]);
+        acc[r] += w4.x * t0 + w4.y * t1 + w4.z * t2 + w4.w * t3;
+      }
+    }
+  }
+  if (j < W) {
+    const float ab = a[b];
+    const float cb = (transpose || !c) ? 0.f : c[b];
+    const bool noisy = !transpose && sigma && eps;
+    const float sb = noisy ? sigma[b] : 0.f;
+    const bool masked = !transpose && cut;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (r < rpt) {
+        const int i = ig * rpt + r;
+        const int64_t o = ((int64_t)b * H + i) * W + j;
+        float v = ab * acc[r] + cb;
+        if (noisy) v = fmaf(sb, eps[o], v);
+        if (masked && !ada_cut_keep(c4, i, j, H, W)) v = 0.f;
+        y[o] = v;
+      }
+  }
+}
+
 }  // namespace
 
 extern "C" int dgv2_upfirdn2d(void* out, const void* in, const float* kernel, int major, int in_h, int in_w, int minor,
@@ -216,6 +364,24 @@ extern "C" int dgv2_ada_apply(float* y, const float* x, const float* Ay, const f
   if (!no_lds && H <= ADA_HMAX && H % 4 == 0 && K <= ADA_KMAX)
     ada_apply_lds_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(y, x, Ay, kx, off, sgn, a, c, H, W, K, transpose);
   else
-    ada_apply_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(y, x, Ay, kx, off, sgn, a, c, H, W, K, transpose);
+    ada_apply_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(y, x, Ay, kx, off, sgn, a, c, nullptr, nullptr, nullptr, H, W, K,
+                                                              transpose);
+  DGV2_RETURN_LAST();
+}
+
+extern "C" int dgv2_ada_apply_img(float* y, const float* x, const float* Ay, const float* kx, const int* off,
+                                  const int* sgn, const float* a, const float* c, const float* cut, const float* sigma,
+                                  const float* eps, int B, int H, int W, int K, int transpose, void* stream) {
+  if (!y || !x || !Ay || !kx || !off || !sgn || !a || B <= 0 || H <= 0 || W <= 0 || K <= 0) return DGV2_EINVAL;
+  if ((sigma == nullptr) != (eps == nullptr)) return DGV2_EINVAL;
+  const size_t lds = sizeof(float) * (size_t)H * ADA_TW;
+  if (lds > 64 * 1024) return DGV2_EINVAL;
+  dim3 grid((W + ADA_TW - 1) / ADA_TW, B);
+  static const bool no_lds = getenv("DGV2_NO_ADA_LDS") != nullptr;   // A/B switch for benchmarking
+  if (!no_lds && H <= ADA_HMAX && H % 4 == 0 && K <= ADA2_KMAX)
+    ada_apply_img_lds_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(y, x, Ay, kx, off, sgn, a, c, cut, sigma, eps, H, W, K,
+                                                                    transpose);
+  else
+    ada_apply_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(y, x, Ay, kx, off, sgn, a, c, cut, sigma, eps, H, W, K, transpose);
   DGV2_RETURN_LAST();
 }

@@ -12,6 +12,14 @@
 //   ada_build  : Ay [B,H,H] = D_y S_y(b) M1y  and the K-tap circular x-filter (kx, off, sgn) = one row of
 //                D_x S_x(b) M1x, where M1 = (up-FIR o pad) and D = down-FIR are geometry constants and
 //                S(b) is 1-D linear interpolation at the sample's affine positions (zero outside).
+//
+// reference: the image-space stages of AdaptiveAugment.forward, gans/augment/adaptive_augment.py:547-621.
+//
+//   ada_sample_img : per sample, the four band gains g (sequential power normalisation, :556-572), the noise
+//                    strength sigma (:598-604) and the cutout box (:608-615) from raw draws u2 [B,8], n2 [B,8].
+//   ada_fold       : composes the per-sample band filter h = g @ Hz_fbank (:575) into the operators ada_build made:
+//                    rows Ay' = Fy Ay (Fy: reflect-padded correlation with h, :588,592-594), columns kx' = kx * h
+//                    (circular, :587,589-591) and the offset c' = c (sum h)^2.
 #include "common.h"
 
 namespace {
@@ -242,6 +250,94 @@ __global__ __launch_bounds__(256) void ada_build_kernel(float* __restrict__ Ay, 
   else ada_build_kx_block(kx, off, sgn, gaff, M1x, taps, W, K, blockIdx.y, row);
 }
 
+constexpr int NU2 = 8, NN2 = 8, FOLD_TMAX = 64;
+
+__global__ void ada_sample_img_kernel(float* __restrict__ g, float* __restrict__ sigma, float* __restrict__ cut,
+                                      const float* __restrict__ u2, const float* __restrict__ n2,
+                                      const float* __restrict__ p_ptr, float m_filter, float m_noise, float m_cutout, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float p = p_ptr[0];
+  const float* ub = u2 + (int64_t)b * NU2;
+  const float* nb = n2 + (int64_t)b * NN2;
+  // band gains: band i is amplified by 2^n with probability p * mul, then the gain vector (1, .., t_i, .., 1) is divided by
+  // its expected power under the 1/f spectrum (10, 1, 1, 1) / 13 and accumulated -- one band after the other
+  const float ep[4] = {10.f / 13.f, 1.f / 13.f, 1.f / 13.f, 1.f / 13.f};
+  float gg[4] = {1.f, 1.f, 1.f, 1.f};
+  if (m_filter > 0.f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float ti = ub[i] < m_filter * p ? exp2f(nb[i]) : 1.f;
+      float pw = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pw += ep[k] * (k == i ? ti * ti : 1.f);
+      const float inv = 1.f / sqrtf(pw);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) gg[k] *= (k == i ? ti : 1.f) * inv;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g[b * 4 + k] = gg[k];
+  sigma[b] = (m_noise > 0.f && ub[4] < m_noise * p) ? fabsf(nb[4]) * 0.1f : 0.f;
+  const float size = (m_cutout > 0.f && ub[5] < m_cutout * p) ? 0.5f : 0.f;
+  cut[b * 4 + 0] = ub[6];
+  cut[b * 4 + 1] = ub[7];
+  cut[b * 4 + 2] = size;
+  cut[b * 4 + 3] = size;
+}
+
+// F.pad(mode="reflect") index (no edge repeat) for -(L-1) <= i <= 2(L-1)
+__device__ __forceinline__ int reflect_index(int i, int L) {
+  if (i < 0) i = -i;
+  if (i > L - 1) i = 2 * (L - 1) - i;
+  return i;
+}
+
+// blocks (i < H, b): row i of Ay' = Fy Ay, Fy[i][reflect(i + u - P)] += h[u]  (F.conv2d is a correlation, P = (T-1)/2)
+// blocks (H, b)    : the composite circular taps.  With v[j] = sum_t kx[t] x[(s j + off + t) mod W] the filtered row is
+//     z[j] = sum_u h[u] v[(j + u - P) mod W] = sum_{t,u} kx[t] h[u] x[(s j + (off - P) + t + s (u - P) + P) mod W]:
+//     s = +1 adds u to the tap index, s = -1 adds 2P - u = T - 1 - u.  So kx' = kx * h (full convolution, K + T - 1 taps) for
+//     an unflipped sample and kx * flip(h) for a flipped one, and off' = off - P either way.
+__global__ __launch_bounds__(128) void ada_fold_kernel(float* __restrict__ Ay2, float* __restrict__ kx2, int* __restrict__ off2,
+                                                       float* __restrict__ c2, const float* __restrict__ Ay,
+                                                       const float* __restrict__ kx, const int* __restrict__ off,
+                                                       const int* __restrict__ sgn, const float* __restrict__ c,
+                                                       const float* __restrict__ g, const float* __restrict__ fbank, int H,
+                                                       int W, int K, int NB, int T) {
+  __shared__ float hl[FOLD_TMAX];
+  const int b = blockIdx.y, P = (T - 1) / 2;
+  for (int u = threadIdx.x; u < T; u += blockDim.x) {
+    float acc = 0.f;
+    for (int k = 0; k < NB; ++k) acc += g[(int64_t)b * NB + k] * fbank[k * T + u];
+    hl[u] = acc;
+  }
+  __syncthreads();
+  if ((int)blockIdx.x < H) {
+    const int i = blockIdx.x;
+    const float* Ab = Ay + (int64_t)b * H * H;
+    for (int col = threadIdx.x; col < H; col += blockDim.x) {
+      float acc = 0.f;
+      for (int u = 0; u < T; ++u) acc += hl[u] * Ab[reflect_index(i + u - P, H) * H + col];
+      Ay2[((int64_t)b * H + i) * H + col] = acc;
+    }
+    return;
+  }
+  const int sg = sgn[b], K2 = K + T - 1;
+  const float* kb = kx + (int64_t)b * K;
+  for (int m = threadIdx.x; m < K2; m += blockDim.x) {
+    float acc = 0.f;
+    const int t0 = m - (T - 1) > 0 ? m - (T - 1) : 0, t1 = m < K - 1 ? m : K - 1;
+    for (int t = t0; t <= t1; ++t) acc += kb[t] * hl[sg > 0 ? m - t : T - 1 - (m - t)];
+    kx2[(int64_t)b * K2 + m] = acc;
+  }
+  if (threadIdx.x == 0) {
+    float sum = 0.f;
+    for (int u = 0; u < T; ++u) sum += hl[u];
+    off2[b] = floormod(off[b] - P, W);
+    c2[b] = c[b] * sum * sum;   // ring and reflect padding both preserve a constant
+  }
+}
+
 }  // namespace
 
 // u fp32 [B,16] uniforms in [0,1), n fp32 [B,8] standard normals, p fp32 [1] (device), policy fp32 [11] HOST
@@ -268,5 +364,29 @@ extern "C" int dgv2_ada_build(float* Ay, float* kx, int* off, int* sgn, const fl
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(H + 1, B);
   ada_build_kernel<<<grid, 256, sizeof(float) * W, st>>>(Ay, kx, off, sgn, gaff, M1y, M1x, taps, H, W, K);
+  DGV2_RETURN_LAST();
+}
+
+// u2 fp32 [B,8] uniforms in [0,1): 0-3 band selects, 4 noise select, 5 cutout select, 6-7 cutout centre (x, y);
+// n2 fp32 [B,8] standard normals: 0-3 band log2-gains, 4 sigma (5-7 unused); p fp32 [1] (device);
+// policy_host = HOST array (imgfilter, noise, cutout multipliers).  Outputs g [B,4], sigma [B], cut [B,4].
+extern "C" int dgv2_ada_sample_img(float* g, float* sigma, float* cut, const float* u2, const float* n2, const float* p,
+                                   const float* policy_host, int B, void* stream) {
+  if (!g || !sigma || !cut || !u2 || !n2 || !p || !policy_host || B <= 0) return DGV2_EINVAL;
+  ada_sample_img_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(g, sigma, cut, u2, n2, p, policy_host[0], policy_host[1],
+                                                                       policy_host[2], B);
+  DGV2_RETURN_LAST();
+}
+
+// (Ay [B,H,H], kx [B,K], off [B], sgn [B], c [B]) + band gains g [B,NB] and the bank fbank [NB,T] (T odd) ->
+// Ay2 [B,H,H], kx2 [B,K+T-1], off2 [B], c2 [B].  The reflect padding of (T-1)/2 needs H > (T-1)/2.
+extern "C" int dgv2_ada_fold(float* Ay2, float* kx2, int* off2, float* c2, const float* Ay, const float* kx, const int* off,
+                             const int* sgn, const float* c, const float* g, const float* fbank, int B, int H, int W, int K,
+                             int NB, int T, void* stream) {
+  if (!Ay2 || !kx2 || !off2 || !c2 || !Ay || !kx || !off || !sgn || !c || !g || !fbank) return DGV2_EINVAL;
+  if (B <= 0 || H <= 0 || W <= 0 || K <= 0 || NB <= 0 || T <= 0 || T % 2 == 0 || T > FOLD_TMAX || (T - 1) / 2 > H - 1)
+    return DGV2_EINVAL;
+  dim3 grid(H + 1, B);
+  ada_fold_kernel<<<grid, 128, 0, (hipStream_t)stream>>>(Ay2, kx2, off2, c2, Ay, kx, off, sgn, c, g, fbank, H, W, K, NB, T);
   DGV2_RETURN_LAST();
 }

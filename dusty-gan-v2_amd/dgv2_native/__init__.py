@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libdgv2.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -156,6 +156,9 @@ SIGNATURES = {
     "dgv2_ada_apply": [_c_ptr] * 8 + [_c_int] * 5 + [_c_ptr],
     "dgv2_ada_sample": [_c_ptr] * 7 + [_c_int] * 3 + [_c_ptr],
     "dgv2_ada_build": [_c_ptr] * 8 + [_c_int] * 4 + [_c_ptr],
+    "dgv2_ada_sample_img": [_c_ptr] * 7 + [_c_int, _c_ptr],
+    "dgv2_ada_fold": [_c_ptr] * 11 + [_c_int] * 6 + [_c_ptr],
+    "dgv2_ada_apply_img": [_c_ptr] * 11 + [_c_int] * 5 + [_c_ptr],
     "dgv2_coords_convert": [_c_ptr] * 4 + [_c_int] * 3 + [_c_f32] * 3 + [_c_int, _c_ptr],
     "dgv2_msml_prepare": [_c_ptr] * 6 + [_c_int] * 5 + [_c_ptr],
     "dgv2_msml_fwd": [_c_ptr] * 7 + [_c_int] * 7 + [_c_ptr],

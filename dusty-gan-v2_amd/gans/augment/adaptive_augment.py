@@ -20,6 +20,12 @@ padding (proved equivalent to the data-dependent padding in tests/test_oracle_go
 module has static shapes, no host synchronisation, and is hipGraph-capturable.  The image itself
 is read once and written once by dgv2_ada_apply; first and second derivatives w.r.t. the image
 are the same kernel with the transposed operators.
+
+The image-space stages (band filter, additive noise, cutout; reference :547-621) are linear in the
+image as well and ride in the same launch: the per-sample 43-tap band filter (circular along W,
+reflect along H) is composed into (Ay, kx, off, c) by dgv2_ada_fold, the noise is an additive term
+and the cutout an output mask of dgv2_ada_apply_img (DESIGN.md "ADA image-space stages").  With the
+three multipliers at zero, forward takes the launches above and nothing else.
 """
 import math
 
@@ -95,10 +101,11 @@ class AdaptiveAugment(torch.nn.Module):
                         iso_scale=float(iso_scale), frac_trans=float(frac_trans), brightness=float(brightness),
                         contrast=float(contrast), luma_flip=float(luma_flip), hue=float(hue),
                         saturation=float(saturation))
-        if float(imgfilter) > 0 or float(noise) > 0 or float(cutout) > 0:
-            raise NotImplementedError("imgfilter / noise / cutout are off in dusty_v2.yaml and not built")
+        self.mul_img = dict(imgfilter=float(imgfilter), noise=float(noise), cutout=float(cutout))
+        self.imgfilter_bands = [1, 1, 1, 1]
+        self.imgfilter_std = 1
         self.h_trans_factor = 0.0 if ada_kwargs.get("wonly_trans", False) else 1.0
-        # image-space filter bank buffer, kept for state-dict compatibility (adaptive_augment.py:351-366)
+        # image-space filter bank (adaptive_augment.py:351-366)
         Hz_lo = np.asarray(SYM2)
         Hz_hi = Hz_lo * ((-1) ** np.arange(Hz_lo.size))
         Hz_lo2 = np.convolve(Hz_lo, Hz_lo[::-1]) / 2
@@ -304,28 +311,75 @@ class AdaptiveAugment(torch.nn.Module):
         """img [B,1,H,W] -> augmented [B,1,H,W] (fp32).  `draws` optionally injects
         {"G": [B,3,3], "C": [B,4,4]} (parity tests) or the RAW draws {"u": [B,16] uniform, "n": [B,8] normal} of the
         fused sampler (the step bodies make every draw of a body in one launch); otherwise they are sampled on the device.
+        With imgfilter / noise / cutout on, likewise {"g": [B,4], "sigma": [B], "cut": [B,4], "eps": [B,1,H,W]} (parity) or
+        the raw {"u2": [B,8] uniform, "n2": [B,8] normal, "eps": [B,1,H,W] normal} of dgv2_ada_sample_img.
         `out` (no-grad callers): the fp32 tensor to write into (one half of a stacked batch)."""
         B, ch, H, W = img.shape
         if ch != 1:
             raise NotImplementedError("ADA on this path handles 1-channel range images")
         dev = img.device
+        img_on = self.image_space_on()
+        if img_on and (H < 22 or W < 21):
+            raise ValueError(f"imgfilter / noise / cutout pad the image by 21 (reflect along H, circular along W): "
+                             f"{H}x{W} is too small, H >= 22 and W >= 21 are needed")
+        draws = {} if draws is None else draws
         with torch.no_grad():
             M1y, _, M1x, _, taps = self._chain_consts(H, W, dev)
-            if draws is None or "u" in draws:
+            if "G" not in draws:
                 # sampling + colour collapse in one kernel, operators in two (dgv2_ada_sample / _build)
-                raw = {} if draws is None else dict(u=draws["u"], n=draws["n"])
+                raw = dict(u=draws["u"], n=draws["n"]) if "u" in draws else {}
                 gaff, a, c = native.ada_sample(B, H, W, self.p.reshape(1), self.policy_vector(), dev, **raw)
             else:
                 G = draws["G"].to(dev).float()
                 gaff = torch.stack([G[:, 0, 0], G[:, 0, 2], G[:, 1, 1], G[:, 1, 2]], dim=1).contiguous()
                 a, c = self.collapse_color(draws["C"].to(dev).float())
             Ay, kx, off, sgn = native.ada_build(gaff, M1y, M1x, taps, H, W, KTAPS)
-        return native.ada_apply(img.float(), Ay, kx, off, sgn, a, c, out=out)
+            if img_on:
+                g, sigma, cut, eps = self._image_space_draws(draws, B, H, W, dev)
+                if g is not None:
+                    Ay, kx, off, c = native.ada_fold(Ay, kx, off, sgn, c, g, self.Hz_fbank, W)
+        if not img_on:
+            return native.ada_apply(img.float(), Ay, kx, off, sgn, a, c, out=out)
+        return native.ada_apply_img(img.float(), Ay, kx, off, sgn, a, c, cut, sigma, eps, out=out)
+
+    def image_space_on(self):
+        return any(v > 0 for v in self.mul_img.values())
+
+    def image_policy_vector(self):
+        return [self.mul_img["imgfilter"], self.mul_img["noise"], self.mul_img["cutout"]]
+
+    def _image_space_draws(self, draws, B, H, W, dev):
+        """(g [B,4], sigma [B], cut [B,4], eps [B,1,H,W]) of the image-space stages; a stage whose multiplier is zero gets
+        None and costs nothing in the apply."""
+        m = self.mul_img
+        if "g" in draws or "sigma" in draws or "cut" in draws:
+            def get(k):
+                return draws[k].to(dev).float().reshape(B, -1).contiguous()
+            g = get("g") if m["imgfilter"] > 0 else None
+            sigma = get("sigma").reshape(B) if m["noise"] > 0 else None
+            cut = get("cut") if m["cutout"] > 0 else None
+        else:
+            raw = dict(u2=draws["u2"], n2=draws["n2"]) if "u2" in draws else {}
+            g, sigma, cut = native.ada_sample_img(B, self.p.reshape(1), self.image_policy_vector(), dev, **raw)
+            g = g if m["imgfilter"] > 0 else None
+            sigma = sigma if m["noise"] > 0 else None
+            cut = cut if m["cutout"] > 0 else None
+        eps = None
+        if sigma is not None:
+            eps = draws["eps"].to(dev).float().contiguous() if "eps" in draws else torch.randn(B, 1, H, W, device=dev)
+            if tuple(eps.shape) != (B, 1, H, W):
+                raise ValueError(f"eps {tuple(eps.shape)} for an image batch {(B, 1, H, W)}")
+        return g, sigma, cut, eps
 
     def policy_vector(self):
         m = self.mul
         return [m["lr_flip"], m["ud_flip"], m["int_trans"], m["iso_scale"], m["frac_trans"], m["brightness"],
                 m["contrast"], m["luma_flip"], m["hue"], m["saturation"], self.h_trans_factor]
+
+    @torch.no_grad()
+    def sample_image_params(self, B, device):
+        """(g [B,4], sigma [B], cut [B,4]) drawn by the fused image-space sampler (the path `forward` uses)."""
+        return native.ada_sample_img(B, self.p.reshape(1), self.image_policy_vector(), device)
 
     @torch.no_grad()
     def sample_params(self, B, H, W, device):

@@ -202,6 +202,80 @@ def ada_build(gaff, M1y, M1x, taps, H, W, K):
 
 
 # ---------------------------------------------------------------------------------------
+# ADA image-space stages: band filter, additive noise, cutout (reference: gans/augment/adaptive_augment.py:547-621)
+# ---------------------------------------------------------------------------------------
+class _AdaApplyImg(Function):
+    """y = mask * (a * (Ay x Cx^T) + c + sigma * eps) in one launch.  Backward is the adjoint (mask on the cotangent, no
+    additive terms); double backward is the forward without c and without the noise."""
+
+    @staticmethod
+    def forward(ctx, x, Ay, kx, off, sgn, a, c, cut, sigma, eps, transpose, out=None):
+        x = x.contiguous().float()
+        B, _, H, W = x.shape
+        N.check(x, Ay, kx, off, sgn, a, c, cut, sigma, eps, out)
+        if out is not None and (out.shape != x.shape or out.dtype != torch.float32):
+            raise ValueError("ada_apply_img: `out` must be a contiguous fp32 tensor shaped like the input")
+        if eps is not None and (eps.numel() != x.numel() or eps.dtype != torch.float32):
+            raise ValueError("ada_apply_img: `eps` must be an fp32 tensor with one normal per pixel")
+        y = torch.empty_like(x) if out is None else out
+        N.call("dgv2_ada_apply_img", N.ptr(y), N.ptr(x), N.ptr(Ay), N.ptr(kx), N.ptr(off), N.ptr(sgn), N.ptr(a), N.ptr(c),
+               N.ptr(cut), N.ptr(sigma), N.ptr(eps), B, H, W, kx.shape[1], int(transpose), N.stream())
+        ctx.save_for_backward(Ay, kx, off, sgn, a, cut)
+        ctx.transpose = transpose
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        Ay, kx, off, sgn, a, cut = ctx.saved_tensors
+        gx = _AdaApplyImg.apply(g, Ay, kx, off, sgn, a, None, cut, None, None, not ctx.transpose)
+        return (gx,) + (None,) * 11
+
+
+def ada_apply_img(x, Ay, kx, off, sgn, a, c, cut=None, sigma=None, eps=None, out=None):
+    """ada_apply with the image-space terms: cut [B,4] (centre x, centre y, size x, size y), sigma [B] and the normal field
+    eps [B,1,H,W] (both or neither); the operators may be the folded ones of ada_fold.  `out` as in ada_apply."""
+    if out is not None and torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("ada_apply_img(out=...) is for passes that record no graph")
+    if (sigma is None) != (eps is None):
+        raise ValueError("ada_apply_img: sigma and eps come together")
+    return _AdaApplyImg.apply(x, Ay, kx, off, sgn, a, c, cut, sigma, eps, False, out)
+
+
+def ada_sample_img(B, p, policy, device, u2=None, n2=None):
+    """Draw the band gains g [B,4], the noise strength sigma [B] and the cutout box cut [B,4] in one kernel.
+    policy: (imgfilter, noise, cutout) multipliers.  u2 [B,8] uniform / n2 [B,8] normal: the raw draws (slot layout in
+    include/dgv2.h), when the caller made them already."""
+    u2 = torch.rand(B, 8, device=device) if u2 is None else u2.float().contiguous()
+    n2 = torch.randn(B, 8, device=device) if n2 is None else n2.float().contiguous()
+    if tuple(u2.shape) != (B, 8) or tuple(n2.shape) != (B, 8):
+        raise ValueError(f"ada_sample_img: u2 {tuple(u2.shape)} / n2 {tuple(n2.shape)} for B = {B}")
+    N.check(u2, n2, p)
+    g = torch.empty((B, 4), device=device, dtype=torch.float32)
+    sigma = torch.empty(B, device=device, dtype=torch.float32)
+    cut = torch.empty((B, 4), device=device, dtype=torch.float32)
+    pol = (_ct.c_float * 3)(*policy)
+    N.call("dgv2_ada_sample_img", N.ptr(g), N.ptr(sigma), N.ptr(cut), N.ptr(u2), N.ptr(n2), N.ptr(p), pol, B, N.stream())
+    return g, sigma, cut
+
+
+def ada_fold(Ay, kx, off, sgn, c, g, fbank, W):
+    """Compose the per-sample band filter g @ fbank into the operators of ada_build: (Ay', kx' [B,K+T-1], off', c')."""
+    B, H, _ = Ay.shape
+    NB, T = fbank.shape
+    K = kx.shape[1]
+    if tuple(g.shape) != (B, NB):
+        raise ValueError(f"ada_fold: g {tuple(g.shape)} for {NB} bands and B = {B}")
+    N.check(Ay, kx, off, sgn, c, g, fbank)
+    Ay2 = torch.empty_like(Ay)
+    kx2 = torch.empty((B, K + T - 1), device=Ay.device, dtype=torch.float32)
+    off2 = torch.empty_like(off)
+    c2 = torch.empty_like(c)
+    N.call("dgv2_ada_fold", N.ptr(Ay2), N.ptr(kx2), N.ptr(off2), N.ptr(c2), N.ptr(Ay), N.ptr(kx), N.ptr(off), N.ptr(sgn),
+           N.ptr(c), N.ptr(g), N.ptr(fbank), B, H, W, K, NB, T, N.stream())
+    return Ay2, kx2, off2, c2
+
+
+# ---------------------------------------------------------------------------------------
 def upfirdn2d_raw(x4, kernel, up, down, pad):
     """x4 [major, H, W, minor] (reference extension ABI, upfirdn2d.cpp:17-31)."""
     major, in_h, in_w, minor = x4.shape

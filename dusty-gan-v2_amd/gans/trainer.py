@@ -50,6 +50,10 @@ def ema_inplace(ema_model, new_model, decay):
     torch._foreach_copy_(eb, nb)
 
 
+# per-site keys of AdaptiveAugment.forward's `draws`: parity forms (G, C / g, sigma, cut) and raw forms (u, n / u2, n2), eps
+_ADA_DRAW_KEYS = ("G", "C", "u", "n", "g", "sigma", "cut", "u2", "n2", "eps")
+
+
 class Trainer:
     def __init__(self, cfg, sync_scalars=True):
         self.cfg = cfg
@@ -274,7 +278,8 @@ class Trainer:
     def set_draws(self, draws):
         """Inject the random numbers of the NEXT iteration, keyed by call site as in tests/golden/make_golden.py
         (TRAINER_SITES): g.z, g.shifts, g.u, g.keep, g.ada.{G,C}, d.z, d.shifts, d.u, d.keep_real, d.keep_fake,
-        d.ada_real.{G,C}, d.ada_fake.{G,C}, r1.keep, r1.ada.{G,C}.  The values are copied into static device buffers
+        d.ada_real.{G,C}, d.ada_fake.{G,C}, r1.keep, r1.ada.{G,C}; with ADA's image-space stages on, every ada site also takes
+        .{g,sigma,cut,eps} or the raw .{u2,n2,eps} (AdaptiveAugment.forward).  The values are copied into static device buffers
         that the step bodies read, so injected runs replay as hipGraphs as well.  None restores on-device sampling."""
         if draws is None:
             self._injected = None
@@ -314,6 +319,11 @@ class Trainer:
         for site in sites:
             add(site + ".u", (B, 16), native.RNG_UNIFORM, 0.0, 1.0)                # adaptive_augment.py:386-470
             add(site + ".n", (B, 8), native.RNG_NORMAL, 0.0, 1.0)
+            if self.A.image_space_on():                                            # adaptive_augment.py:547-621
+                add(site + ".u2", (B, 8), native.RNG_UNIFORM, 0.0, 1.0)
+                add(site + ".n2", (B, 8), native.RNG_NORMAL, 0.0, 1.0)
+                if self.A.mul_img["noise"] > 0:
+                    add(site + ".eps", (B, 1, H, W), native.RNG_NORMAL, 0.0, 1.0)
         if self._warm() and float(self.cfg.training.warmup.dropout_init_ratio) > 0.0:
             ksites = {"g": ["g.keep"] + (["g.keep_real"] if self.use_real_in_g else []),
                       "d": ["d.keep_real", "d.keep_fake"], "r1": ["r1.keep"]}[body]
@@ -345,13 +355,11 @@ class Trainer:
         return None
 
     def _ada(self, site):
-        if self._injected is not None:
-            if site + ".G" not in self._injected:
-                return None
-            return {"G": self._injected[site + ".G"], "C": self._injected[site + ".C"]}
-        if self._body is not None and site + ".u" in self._body:
-            return {"u": self._body[site + ".u"], "n": self._body[site + ".n"]}
-        return None
+        src = self._injected if self._injected is not None else self._body
+        if src is None:
+            return None
+        draws = {k: src[site + "." + k] for k in _ADA_DRAW_KEYS if site + "." + k in src}
+        return draws or None
 
     # ------------------------------------------------------------------ sub-steps
     # Each sub-step is split into a forward/backward body (`*_fb`), the gradient all-reduce (eager,

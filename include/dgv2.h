@@ -753,6 +753,34 @@ int dgv2_ada_sample(float* gaff, float* a, float* c, const float* u, const float
 int dgv2_ada_build(float* Ay, float* kx, int* off, int* sgn, const float* gaff, const float* M1y,
                    const float* M1x, const float* taps, int B, int H, int W, int K, void* stream);
 
+/* ADA image-space stages: band filter, additive noise, cutout.
+ * replaces: the last third of AdaptiveAugment.forward, gans/augment/adaptive_augment.py:547-621.
+ * All three are linear in the image, so they ride in the separable operator form:
+ *   y[b] = mask[b] * (a[b] * (Ay'[b] @ x[b] @ Cx'[b]^T) + c'[b] + sigma[b] * eps[b]).
+ * sample_img: u2 fp32 [B,8] uniforms in [0,1), n2 fp32 [B,8] standard normals, p fp32 [1] (device); policy_host =
+ *   HOST array of 3 floats (imgfilter, noise, cutout multipliers).  Slot layout:
+ *     u2: 0-3 band selects, 4 noise select, 5 cutout select, 6 cutout centre x, 7 cutout centre y;
+ *     n2: 0-3 band log2-gains, 4 sigma (5-7 unused).
+ *   -> g [B,4] band gains (per band, in order: gain 2^n2 or 1, then the whole vector divided by the root of its
+ *   expected power against (10,1,1,1)/13, accumulated by product), sigma [B] = |n2[4]| * 0.1 or 0,
+ *   cut [B,4] = (centre x, centre y, size x, size y) in units of the image, size 0.5 or 0.
+ * fold: the per-sample band filter h = g @ fbank (fbank fp32 [NB,T], T odd; H > (T-1)/2) composed into the operators of
+ *   dgv2_ada_build: Ay2 = Fy Ay (Fy: correlation with h over the reflect-padded rows), kx2 [B,K+T-1] = kx * h (h
+ *   flipped for a sample with sgn = -1), off2 = off - (T-1)/2 (mod W), c2 = c * (sum h)^2.
+ * apply_img: dgv2_ada_apply with the image-space terms, one read and one write of the image.  cut (fp32 [B,4]),
+ *   sigma (fp32 [B]) + eps (fp32 [B,H,W] standard normals; both or neither) and c may each be NULL.  A pixel (i, j) is
+ *   kept when |(j+0.5)/W - cx| >= sx/2 or |(i+0.5)/H - cy| >= sy/2 (plain distance: the box does not wrap round the
+ *   ring).  transpose = 0: y = mask * (a * (Ay x Cx^T) + c + sigma * eps); transpose = 1 (adjoint): the mask is
+ *   applied to the input, c / sigma / eps are ignored.  Any K; H <= 64, H % 4 == 0, K <= 80 take the LDS kernel. */
+int dgv2_ada_sample_img(float* g, float* sigma, float* cut, const float* u2, const float* n2, const float* p,
+                        const float* policy_host, int B, void* stream);
+int dgv2_ada_fold(float* Ay2, float* kx2, int* off2, float* c2, const float* Ay, const float* kx, const int* off,
+                  const int* sgn, const float* c, const float* g, const float* fbank, int B, int H, int W, int K,
+                  int NB, int T, void* stream);
+int dgv2_ada_apply_img(float* y, const float* x, const float* Ay, const float* kx, const int* off, const int* sgn,
+                       const float* a, const float* c, const float* cut, const float* sigma, const float* eps, int B,
+                       int H, int W, int K, int transpose, void* stream);
+
 /* ---------------------------------------------------------------------------
  * range-image projection
  * replaces: CoordBridge.convert / depth_to_point_map, gans/coords.py:88-185
