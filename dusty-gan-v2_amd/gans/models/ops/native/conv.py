@@ -120,6 +120,24 @@ def _x3_auto_images(wv, fwd):
     return img
 
 
+_CONV1X1 = os.environ.get("DGV2_NO_CONV1X1") is None       # A/B switch: 1x1 stride-1 bf16 convs on conv1x1.hip's streaming GEMM
+
+
+def _conv1x1(entry, out, a, w, B, P, C, O, resid):
+    """The bare 1x1 stride-1 bf16 conv (forward: dgv2_conv1x1_fwd on the [O,C] weights; data gradient: dgv2_conv1x1_dgrad
+    on the transposed [C,O] ones) as a streaming GEMM over the B * P pixels, the residual in its epilogue; False where the
+    switch is off or the kernel does not cover the shape (the direct engine then runs it)."""
+    if not _CONV1X1 or a.dtype != torch.bfloat16 or w.dtype != a.dtype or not w.is_contiguous():
+        return False
+    if resid is not None and (resid.dtype != a.dtype or not resid.is_contiguous()):
+        return False
+    return N.try_call(entry, N.ptr(out), N.ptr(a), N.ptr(w), B, P, C, O, N.ptr(resid), _dt(a), N.stream())
+
+
+def _is_1x1(g):
+    return (g.kh, g.kw, g.stride, g.pad) == (1, 1, 1, 0)
+
+
 def _conv_fwd_raw(x, w, g, bias=None, act=0, alpha=0.2, scale=1.0, resid=None, w8=None, xexact=0):
     """w8: the weight bank's staging image of the same weights (conv_weight_bank(image8=...)): 3x3 ring convs the
     eight-wave engine covers then run dgv2_conv3x3_fwd8 on it.  xexact (fp32 on conv_x3.hip): channels [0, xexact) of x
@@ -139,6 +157,8 @@ def _conv_fwd_raw(x, w, g, bias=None, act=0, alpha=0.2, scale=1.0, resid=None, w
             and N.try_call("dgv2_conv3x3_x3_fwd", N.ptr(y), N.ptr(x), N.ptr(w8), B, H, W, C, min(int(xexact), C), O, N.ptr(bias),
                            N.ptr(resid), act, alpha, scale, N.ptr(N.status_word(x.device)), N.stream())):
         return y     # fp32 on the bf16 matrix cores (three-plane split, six products per multiply: conv_x3.hip)
+    if _is_1x1(g) and bias is None and act == 0 and _conv1x1("dgv2_conv1x1_fwd", y, x, w, B, H * W, C, O, resid):
+        return y     # the residual blocks' skip conv: a plain GEMM, no halo tiles (conv1x1.hip)
     if _direct_ok(g, C % _kstep(x) == 0):
         taps = [(ky - g.pad, kx - g.pad, ky * g.kw + kx) for ky in range(g.kh) for kx in range(g.kw)]
         _conv_taps(y, x, w.reshape(O, g.kh * g.kw, C), Ho, Wo, g.stride, (0, 0), 1, (0, 0), taps, False,
@@ -269,6 +289,10 @@ def _conv_dgrad_raw(gy, w, g, xshape, wt=None, resid=None, w8t=None):
             if N.try_call("dgv2_conv3x3_x3_dgrad", N.ptr(gx), N.ptr(gy), N.ptr(w3t), N.ptr(wt), B, H, W,
                           int(_X3_AUTO[1].get(C, C)), C, O, N.ptr(resid), N.stream()):
                 return gx
+    if _is_1x1(g) and gy.is_contiguous():
+        gx = torch.empty(xshape, device=gy.device, dtype=gy.dtype)
+        if _conv1x1("dgv2_conv1x1_dgrad", gx, gy, wt, B, H * W, C, O, resid):
+            return gx
     even = g.stride == 1 or (H % 2 == 0 and W % 2 == 0)
     if _direct_ok(g, O % _kstep(gy) == 0) and even and not (g.kh == 1 and g.stride == 2):
         return _conv_dgrad_direct(gy, wt.reshape(C, g.kh * g.kw, O), g, xshape, resid)

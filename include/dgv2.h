@@ -681,6 +681,21 @@ int dgv2_conv_taps_ld(void* y, int ldy, const void* x, const void* w, int B, int
                       const int* extras_host, int hzero, int ring, int accumulate, const float* bias,
                       const void* resid, int act, float alpha, float scale, int dtype, void* stream);
 
+/* The 1x1 stride-1 conv as a streaming GEMM over the B * P pixels (conv1x1.hip: the slab's weights stay in LDS, the
+ * activations go from 16-byte global loads straight into the matrix cores, K ascending in one fp32 accumulator, the
+ * residual added to the rounded product: bit for bit what dgv2_conv_taps computes for the same operands):
+ *   dgv2_conv1x1_fwd:    y [B,P,O]  = x [B,P,C]  . wf [O,C]^T (+ resid [B,P,O])
+ *   dgv2_conv1x1_dgrad:  gx [B,P,C] = gy [B,P,O] . wt [C,O]^T (+ resid [B,P,C])
+ * wf / wt: the weight bank's forward / transposed layouts (dgv2_conv_weight_bank; any runtime scale already folded in);
+ * no bias, no activation.  DGV2_BF16, C % 32 == 0, O % 32 == 0, contraction length (C forward, O data gradient) <= 512,
+ * 16-byte aligned pointers; DGV2_ENOTSUP otherwise: callers then run dgv2_conv_taps on the same operands.
+ * replaces: ops.Conv2d forward / data gradient (gans/models/ops/common.py:187-210) of ResidualBlock.skip behind its
+ *   decimating blur (gans/models/dusty_v2.py:337-345). */
+int dgv2_conv1x1_fwd(void* y, const void* x, const void* wf, int B, int P, int C, int O, const void* resid, int dtype,
+                     void* stream);
+int dgv2_conv1x1_dgrad(void* gx, const void* gy, const void* wt, int B, int P, int C, int O, const void* resid,
+                       int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------
  * discriminator stem in one pass: BlurVH -> 1x1 conv (2 -> O) -> bias + leaky ReLU, and its backward.
  * replaces: Discriminator layers[0:3] (dusty_v2.py:364-367) = ops.BlurVH (common.py:141-155) +
