@@ -5,6 +5,7 @@
 //  * range-image projection, reference: gans/coords.py:73-185, gans/trainer.py:211-217;
 //  * sum of squares (input-magnitude EMA of ModConv2d, gans/models/ops/style.py:100-101).
 #include "common.h"
+#include "coords_dev.h"
 
 namespace {
 
@@ -98,17 +99,7 @@ __global__ void ring_shift_adjoint_kernel(float* __restrict__ g_skip, const floa
 }
 
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float inv_depth_norm_from_depth(float d, float min_d, float max_d) {
-  const bool valid = (d >= min_d) && (d <= max_d) && (d > 0.f);
-  return valid ? (1.f / (d + 1e-11f)) * min_d : 0.f;
-}
-
-__device__ __forceinline__ float depth_from_inv_depth_norm(float x, float min_d, float max_d) {
-  const float inv = x / min_d;
-  const bool valid = (inv >= 1.f / max_d) && (inv <= 1.f / min_d) && (inv > 0.f);
-  return valid ? 1.f / (inv + 1e-11f) : 0.f;
-}
-
+// the per-pixel conversions live in coords_dev.h (frame.hip inlines the same functions)
 __global__ void coords_kernel(float* __restrict__ out, const float* __restrict__ in, const float* __restrict__ mask,
                               const float* __restrict__ angle, int B, int HW, float min_d, float max_d,
                               float raydrop_const, int mode) {
@@ -126,16 +117,15 @@ __global__ void coords_kernel(float* __restrict__ out, const float* __restrict__
       out[t] = depth_from_inv_depth_norm(x, min_d, max_d);
     } else {
       float d = x;
-      if (mode == 2) d = (x > 1e-11f) ? depth_from_inv_depth_norm(x, min_d, max_d) : 0.f;
+      if (mode == 2) d = depth_from_inv_depth_norm_tol(x, min_d, max_d);
       const int p = (int)(t % HW);
       const int64_t b = t / HW;
-      float se, ce, sa, ca;
-      sincosf(angle[p], &se, &ce);
-      sincosf(angle[HW + p], &sa, &ca);
+      float px, py, pz;
+      point_from_depth(d, angle[p], angle[HW + p], px, py, pz);
       float* o = out + b * 3 * HW + p;
-      o[0] = d * ce * ca;
-      o[HW] = d * ce * sa;
-      o[2 * (int64_t)HW] = d * se;
+      o[0] = px;
+      o[HW] = py;
+      o[2 * (int64_t)HW] = pz;
     }
   }
 }

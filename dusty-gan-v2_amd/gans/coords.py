@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from gans.geometry import estimate_surface_normal
 from gans.models.ops import native
 
 
@@ -92,7 +93,7 @@ class CoordBridge(nn.Module):
                 return self._k(x, 0) / self.min_depth
             if tgt == T.DEPTH_NORM:
                 return x / self.max_depth
-            if tgt in (T.POINT_MAP, T.POINT_SET):
+            if tgt in (T.POINT_MAP, T.POINT_SET, T.NORMAL_MAP):
                 return self.convert(self._k(x, 3), T.POINT_MAP, tgt)
         elif src == T.DEPTH_NORM:
             return self.convert(x * self.max_depth, T.DEPTH, tgt)
@@ -106,7 +107,7 @@ class CoordBridge(nn.Module):
                 return x / self.min_depth
             if tgt in (T.DEPTH, T.DEPTH_NORM):
                 return self.convert(self._k(x, 1), T.DEPTH, tgt)
-            if tgt in (T.POINT_MAP, T.POINT_SET):
+            if tgt in (T.POINT_MAP, T.POINT_SET, T.NORMAL_MAP):
                 return self.convert(self._k(x, 2), T.POINT_MAP, tgt)
         elif src == T.POINT_MAP:
             if tgt == T.POINT_SET:
@@ -115,6 +116,11 @@ class CoordBridge(nn.Module):
                 return x  # reference quirk (coords.py:157-165): the point map is returned unchanged
             if tgt in (T.DEPTH_NORM, T.INV_DEPTH, T.INV_DEPTH_NORM):
                 return self.convert(torch.norm(x, p=2, dim=1, keepdim=True), T.DEPTH, tgt)
+            if tgt == T.NORMAL_MAP:
+                # coords.py:171-175; no gradient (the reference's callers colour point clouds with it)
+                normals = estimate_surface_normal(x / self.max_depth, d=2).neg_()
+                normals[normals != normals] = 0.0
+                return normals
         raise NotImplementedError(f"{src} to {tgt}")
 
     def depth_to_point_map(self, depth):

@@ -18,3 +18,4 @@ from .modlayer import *  # noqa: F401,F403
 from .misc import *  # noqa: F401,F403
 from .second_order import *  # noqa: F401,F403
 from .inversion import *  # noqa: F401,F403
+from .frame import *  # noqa: F401,F403

@@ -1,5 +1,6 @@
-"""Training-path utilities (reference: gans/utils.py:21-42, 85-105, 238-271).  Visualisation helpers
-of the reference file are out of scope."""
+"""Training-path utilities (reference: gans/utils.py:21-42, 85-105, 238-271) and the visualisation helpers a latent
+walk needs: cycle, colorize, points_to_normal_2d (utils.py:136-138, 167-202).  The rest of the reference file's
+visualisation code (video writers, spectra) is out of scope."""
 import os
 import random
 
@@ -39,6 +40,51 @@ def sigmoid_to_tanh(x):
 def tanh_to_sigmoid(x):
     """[-1,+1] -> [0,1]"""
     return (x + 1.0) / 2.0
+
+
+def cycle(iterable):
+    while True:
+        yield from iterable
+
+
+_LUTS = {}   # (colormap name, device) -> [256,3] fp32 on that device
+
+
+def _named_lut(cmap, device):
+    key = (cmap, torch.device(device))
+    if key not in _LUTS:
+        import matplotlib   # only a NAME needs it, and only the first time per device
+        try:
+            colormap = matplotlib.colormaps[cmap]
+        except KeyError:
+            raise ValueError(f"unknown cmap: {cmap}") from None
+        colors = colormap(np.linspace(0, 1, 256))[:, :3]
+        _LUTS[key] = torch.tensor(colors, device=device).float()
+    return _LUTS[key]
+
+
+def colorize(tensor, cmap="turbo"):
+    """(B,1,H,W) or (B,H,W) in [0,1] -> (B,3,H,W) colours (reference: utils.py:167-191), one launch (dgv2_colorize).
+    cmap: an ndarray [N,3], or the name of a matplotlib colormap (sampled at 256 points, cached per device)."""
+    from gans.models.ops import native
+    if tensor.ndim == 4:
+        B, C, H, W = tensor.shape
+        assert C == 1, f"expected (B,1,H,W) tensor, but got {tensor.shape}"
+        tensor = tensor.squeeze(1)
+    assert tensor.ndim == 3, f"got {tensor.ndim}!=3"
+    if isinstance(cmap, np.ndarray):
+        lut = torch.tensor(cmap, device=tensor.device).float()
+    else:
+        lut = _named_lut(cmap, tensor.device)
+    return native.colorize_lut(tensor, lut)
+
+
+def points_to_normal_2d(points_map, mode="closest", d=2):
+    """(B,3,H,W) points -> normal colours in [0,1] (reference: utils.py:198-202)."""
+    from gans.geometry import estimate_surface_normal
+    normals = estimate_surface_normal(points_map, d=d, mode=mode).neg_()
+    normals[normals != normals] = 0.0
+    return tanh_to_sigmoid(normals).clamp_(0.0, 1.0)
 
 
 class InfiniteSampler(torch.utils.data.Sampler):

@@ -1032,6 +1032,24 @@ int dgv2_fourier_feature_bwd(float* g_angle, const void* g, const float* angle, 
                              const float* phase, int B, int Ba, int H, int W, int F, int ld, int c0, int dtype,
                              void* stream);
 
+/* ---------------------------------------------------------------------------
+ * frame post-processing of a latent walk (gans/interpolation.py)
+ * replaces: demo_interpolation.py:79-86 (tanh_to_sigmoid, CoordBridge.convert to a point map, kornia median_blur
+ *   (3, 3), convert to a normal map, tanh_to_sigmoid, / max_depth, two rearranges) -- ONE launch.
+ * image fp32 [B,1,H,W] in [-1,1] (the generator's "image"), angle fp32 [1,2,H,W] ->
+ *   points fp32 [B,H*W,3] = median3x3(point_map((image + 1) / 2)) / max_depth, the conversion being that of
+ *   dgv2_coords_convert mode 2; colors fp32 [B,H*W,3] = (1 - n) / 2 with n the dgv2_surface_normal (d = 2, "closest")
+ *   of points, NaN -> 0.
+ * border: what the median's window sees outside the image: 0 zeros (kornia), 1 replicate rows / circular columns.
+ *   The normal's neighbour at a clamped row / wrapped column is the median AT that pixel under this rule.
+ * DGV2_EINVAL where dgv2_surface_normal rejects (W <= 2, empty shapes, null pointers) and for another border.
+ * ------------------------------------------------------------------------- */
+int dgv2_frame_points(float* points, float* colors, const float* image, const float* angle, int B, int H, int W,
+                      float min_depth, float max_depth, int border, void* stream);
+/* Colour lookup.  replaces: colorize, gans/utils.py:167-191 (mul, clamp, long, embedding, permute).
+ * x fp32 [B,H,W], lut fp32 [n_colors,3] -> out fp32 [B,3,H,W] = lut[(long) clamp(x * n_colors, 0, n_colors - 1)]. */
+int dgv2_colorize(float* out, const float* x, const float* lut, int B, int H, int W, int n_colors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
