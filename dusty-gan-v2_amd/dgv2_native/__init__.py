@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libdgv2.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -169,6 +169,9 @@ SIGNATURES = {
     "dgv2_fourier_feature_bwd": [_c_ptr] * 6 + [_c_int] * 8 + [_c_ptr],
     "dgv2_frame_points": [_c_ptr] * 4 + [_c_int] * 3 + [_c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_colorize": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr],
+    "dgv2_crf_rnn_forward": [_c_ptr] * 11 + [_c_int] * 7 + [_c_ptr],
+    "dgv2_crf_rnn_backward_scratch": [_c_ptr] + [_c_int] * 5,
+    "dgv2_crf_rnn_backward": [_c_ptr] * 5 + [_c_i64] + [_c_ptr] * 11 + [_c_int] * 7 + [_c_ptr],
 }
 
 

@@ -19,3 +19,4 @@ from .misc import *  # noqa: F401,F403
 from .second_order import *  # noqa: F401,F403
 from .inversion import *  # noqa: F401,F403
 from .frame import *  # noqa: F401,F403
+from .crf import *  # noqa: F401,F403

@@ -1050,6 +1050,46 @@ int dgv2_frame_points(float* points, float* colors, const float* image, const fl
  * x fp32 [B,H,W], lut fp32 [n_colors,3] -> out fp32 [B,3,H,W] = lut[(long) clamp(x * n_colors, 0, n_colors - 1)]. */
 int dgv2_colorize(float* out, const float* x, const float* lut, int B, int H, int W, int n_colors, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * CRF-RNN refinement layer of the range-image segmentation models (crf.hip; semseg/models/crf_as_rnn.py here)
+ * replaces: CRFRNN.forward and autograd through it, semseg/models/crf_as_rnn.py:110-132 (F.unfold + einops + a Python
+ *   loop over samples over a materialised [B,C,K-1,H*W] bilateral kernel).
+ * All fp32, NCHW.  unary U [B,C,H,W], xyz [B,3,H,W], mask m [B,H,W] (multiplied in; may be non-binary),
+ * kernel_gamma / kernel_alpha [C,C,kh,kw] (only the diagonal [c,c] is read: g_c, a_c), theta_beta [C],
+ * weight_smoothness ws / weight_appearance wa [C], compat M [C,C] (label_compatibility.weight[:, :, 0, 0]).
+ * n runs over the kh*kw window offsets; a position outside the image contributes 0.  Q = U, then num_iters times
+ *   P      = softmax(Q, dim=1)
+ *   S_c(p) = sum_n g_c(n) P_c(p+n)                L_c(p) = sum_n a_c(n) P_c(p+n)      (centre taps read from the buffers)
+ *   A_c(p) = m(p) sum_{n != 0} beta_c(p,n) m(p+n) P_c(p+n),   beta_c(p,n) = exp(-|xyz(p+n) - xyz(p)|^2 / (2 theta_beta[c]^2))
+ *   T_c    = ws[c] S_c + wa[c] A_c L_c
+ *   Q_c    = U_c - sum_c' M[c,c'] T_c'
+ * One launch per iteration; beta is recomputed from xyz staged in LDS.  out [B,C,H,W]; qsave [num_iters-1][B,C,H,W]
+ * receives the inputs Q of iterations 1 .. num_iters-1 (iteration 0's is U), which is what the backward reads (NULL
+ * when num_iters == 1).
+ * Backward of one iteration, given the cotangent dQ' of its output (beta is symmetric, so one gather stencil serves):
+ *   dU += dQ'      dM[c,c'] = -sum_{b,p} dQ'_c T_c'      dT_c' = -sum_c M[c,c'] dQ'_c
+ *   dws[c] = sum_{b,p} dT_c S_c      dwa[c] = sum_{b,p} dT_c A_c L_c      dS = ws dT    dL = wa dT A    dA = wa dT L
+ *   dP_c(q) = sum_n [g_c(-n) dS_c(q+n) + a_c(-n) dL_c(q+n)] + m(q) sum_{n != 0} beta_c(q,n) m(q+n) dA_c(q+n)
+ *   dQ_c    = P_c (dP_c - sum_c' P_c' dP_c')
+ * Two launches per iteration plus one finishing launch: g_unary [B,C,H,W], g_weight_smoothness / g_weight_appearance
+ * [C], g_compat [C,C], all overwritten; the parameter gradients are per-block partial sums in `scratch` (fp32,
+ * >= dgv2_crf_rnn_backward_scratch elements) folded in a fixed order: no float atomics, bit-identical from run to run.
+ * xyz and mask get no gradient (the reference detaches the bilateral kernel; the mask is data).
+ * 1 <= C <= 8; kh, kw odd, kh <= 5, kw <= 9; any H, W >= 1; num_iters >= 1.  DGV2_EINVAL outside that range, for null
+ * pointers, empty shapes and a short scratch.
+ * ------------------------------------------------------------------------- */
+int dgv2_crf_rnn_forward(float* out, float* qsave, const float* unary, const float* xyz, const float* mask,
+                         const float* kernel_gamma, const float* kernel_alpha, const float* theta_beta,
+                         const float* weight_smoothness, const float* weight_appearance, const float* compat, int B,
+                         int C, int H, int W, int kh, int kw, int num_iters, void* stream);
+int dgv2_crf_rnn_backward_scratch(int64_t* elems, int B, int C, int H, int W, int num_iters);
+int dgv2_crf_rnn_backward(float* g_unary, float* g_weight_smoothness, float* g_weight_appearance, float* g_compat,
+                          float* scratch, int64_t scratch_elems, const float* g_out, const float* qsave,
+                          const float* unary, const float* xyz, const float* mask, const float* kernel_gamma,
+                          const float* kernel_alpha, const float* theta_beta, const float* weight_smoothness,
+                          const float* weight_appearance, const float* compat, int B, int C, int H, int W, int kh,
+                          int kw, int num_iters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
