@@ -20,3 +20,4 @@ from .second_order import *  # noqa: F401,F403
 from .inversion import *  # noqa: F401,F403
 from .frame import *  # noqa: F401,F403
 from .crf import *  # noqa: F401,F403
+from .knn import *  # noqa: F401,F403

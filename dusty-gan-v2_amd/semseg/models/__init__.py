@@ -1,3 +1,4 @@
 from .crf_as_rnn import CRFRNN  # noqa: F401
+from .knn import kNN2d  # noqa: F401
 
-__all__ = ["CRFRNN"]
+__all__ = ["CRFRNN", "kNN2d"]

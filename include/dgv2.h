@@ -1090,6 +1090,41 @@ int dgv2_crf_rnn_backward(float* g_unary, float* g_weight_smoothness, float* g_w
                           const float* weight_appearance, const float* compat, int B, int C, int H, int W, int kh,
                           int kw, int num_iters, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * kNN label filter of the range-image segmentation models (knn.hip; semseg/models/knn.py here)
+ * replaces: kNN2d.forward, semseg/models/knn.py:38-76 (the RangeNet++ filter: F.unfold + a K-channel depthwise conv
+ *   over a [B,1,K,H*W] tensor + topk + two gathers + scatter_add_ into [B,1,C+1,H*W] + argmax).
+ * depth fp32 [B,1,H,W], label int64 [B,H,W], dist_kernel fp32 [kh,kw] (the module's buffer) -> out int64 [B,H,W].
+ * All arithmetic in fp32.  K = kh*kw window slots with offsets o_k in row-major order, ph = kh/2, pw = kw/2:
+ *   nb_k(q)   = depth(q + o_k), 0 outside the image (unfold's padding), then +inf where that is < 0; the anchor
+ *               depth(q) is used raw
+ *   jump_k(q) = |nb_k(q) - depth(q)| for q inside the image, 0 for q outside (the conv's padding)
+ *   dist_k(p) = sum_j w(o_j) jump_k(p + o_j)
+ *   w         = 1 - G / sum G,  G(dy,dx) = exp(-(dy^2 + dx^2) / (2 sigma^2)): built by the caller in float32 exactly
+ *               as the reference's get_gaussian_kernel does and passed as dist_kernel
+ * The k slots of smallest dist_k(p) are selected; ties go to the lower slot index (the reference's
+ * topk(sorted=False) leaves ties unspecified: this is the definition here).  A selected slot votes for
+ * label(p + o_k), 0 outside the image; with cutoff > 0 a slot with dist_k(p) > cutoff votes for the discarded bin
+ * instead, and so does a label outside [0, num_classes) (the reference raises there).  out(p) is the class of
+ * [0, num_classes) with the most votes; ties and "no votes" go to the lowest class, as argmax does.
+ * One launch; a block stages depth with a halo of (2 ph, 2 pw) and the labels with a halo of (ph, pw) in LDS and
+ * computes the rest from there; num_classes is unbounded (the vote counts equal labels pairwise).
+ * Supported: kh, kw odd and <= 5 with kh*kw > 1 (a 1 x 1 window has w = 0, hence 0 * inf), 1 <= k <= kh*kw,
+ * num_classes >= 1, any B, H, W >= 1, cutoff not NaN.  DGV2_EINVAL outside that range and for null pointers.
+ * ------------------------------------------------------------------------- */
+int dgv2_knn2d(int64_t* out, const float* depth, const int64_t* label, const float* dist_kernel, int B, int H, int W,
+               int kh, int kw, int k, int num_classes, float cutoff, void* stream);
+/* Confusion counts of a segmentation evaluation (segcount.hip).  replaces: the per-class masked sums of evaluate,
+ * test_semseg.py:23-42, after preds * mask and label * mask of its lines 136-137.
+ * label, pred int64 [n], mask fp32 [n] or NULL; conf int64 [C+1,C+1] is ACCUMULATED INTO (the caller zeroes it once
+ * per evaluation): conf[row(label), col(pred)] += 1 per pixel, where a value of [0,C) is its own row / column and any
+ * other value the last one.  Where mask == 0 both label and prediction count as 0; any other mask value (the
+ * datasets' masks are binary) counts as 1.  tp_c = conf[c,c], fp_c = sum_r conf[r,c] - tp_c, fn_c = sum_r conf[c,r] -
+ * tp_c over all C+1 rows / columns.  Integer atomics only: bit-identical from run to run.
+ * 1 <= num_classes <= 32, 1 <= n < 2^40; DGV2_EINVAL otherwise and for null conf / label / pred. */
+int dgv2_seg_confusion(int64_t* conf, const int64_t* label, const int64_t* pred, const float* mask, int64_t n,
+                       int num_classes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
