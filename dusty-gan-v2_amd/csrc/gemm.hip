@@ -123,10 +123,7 @@ extern "C" int dgv2_bmm_tn(float* gw, const void* gy, const void* x, int B, int 
                            int dtype, void* stream) {
   if (!gw || !gy || !x || B <= 0 || P <= 0 || I <= 0 || O <= 0 || ldgy < O || ldx < I) return DGV2_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  // enough blocks to fill 256 CUs: split the pixel axis when (batch x tiles) is small
-  const int tiles = B * ((O + 63) / 64) * ((I + 127) / 128);
-  int ksplit = 1;
-  while (tiles * ksplit < 512 && P / (ksplit * 2) >= 512) ksplit *= 2;
+  const int ksplit = bmm_tn_ksplit(B, P, I, O);
   if (ksplit > 1) {
     hipError_t e = hipMemsetAsync(gw, 0, sizeof(float) * (size_t)B * O * I, st);
     if (e != hipSuccess) return (int)e;
@@ -178,9 +175,7 @@ extern "C" int dgv2_bmm_tn_cat(float* gw, const void* gy, const void* xa, const 
   if (Ka % ce || Ks % ce || !aligned16(xs) || (Ka > 0 && !aligned16(xa))) return DGV2_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int J = Ka + Ks;
-  const int tiles = B * ((O + 63) / 64) * ((J + 127) / 128);
-  int ksplit = 1;
-  while (tiles * ksplit < 512 && P / (ksplit * 2) >= 512) ksplit *= 2;
+  const int ksplit = bmm_tn_ksplit(B, P, J, O);
   if (ksplit > 1) {
     hipError_t e = hipMemsetAsync(gw, 0, sizeof(float) * (size_t)B * O * J, st);
     if (e != hipSuccess) return (int)e;

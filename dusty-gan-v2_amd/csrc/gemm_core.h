@@ -527,6 +527,16 @@ template <> struct TnFrag<float> {
   }
 };
 
+// The split-K decision of the per-sample weight gradients (dgv2_bmm_tn / dgv2_bmm_tn_cat, and the shapes
+// dgv2_gemm_stream_tn* hands back to them): enough blocks to fill 256 CUs -- split the pixel axis when (batch x tiles) is
+// small.  ONE place: the stream entries are bit-identical to the generic ones only where this returns 1.
+static inline int bmm_tn_ksplit(int B, int P, int J, int O) {
+  const int tiles = B * ((O + 63) / 64) * ((J + 127) / 128);
+  int ksplit = 1;
+  while (tiles * ksplit < 512 && P / (ksplit * 2) >= 512) ksplit *= 2;
+  return ksplit;
+}
+
 template <typename T, int TO, int TJ, class ALoad, class BLoad>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(ALoad al, BLoad bl, float* __restrict__ out, int M, int J,
                                                       int64_t K, int64_t klen, int ksplit, int64_t out_batch_stride,

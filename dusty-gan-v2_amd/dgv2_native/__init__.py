@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libdgv2.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -125,6 +125,12 @@ SIGNATURES = {
     "dgv2_conv_wgrad_direct": [_c_ptr] * 3 + [_c_int] * 10 + [_c_ptr],
     "dgv2_conv1x1_fwd": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr],
     "dgv2_conv1x1_dgrad": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr],
+    "dgv2_gemm_stream_nn": [_c_ptr] * 3 + [_c_int] * 6 + [_c_i64, _c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_ptr, _c_int, _c_int, _c_ptr,
+                            _c_int, _c_ptr, _c_ptr],
+    "dgv2_gemm_stream_nn_cat": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_int, _c_ptr, _c_int,
+                                _c_ptr, _c_ptr],
+    "dgv2_gemm_stream_tn": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr],
+    "dgv2_gemm_stream_tn_cat": [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr],
     "dgv2_bmm_tn_stream_scratch": [_c_ptr] + [_c_int] * 6,
     "dgv2_bmm_tn_stream": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 6 + [_c_ptr],
     "dgv2_bmm_tn_stream_x": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 7 + [_c_ptr],

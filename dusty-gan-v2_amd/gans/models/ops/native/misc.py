@@ -440,8 +440,7 @@ class _ModUpPrepared(Function):
                     gwa = _bmm_tn_stream(gt3, h, B, hl, wl, Ka, Otot)
                 else:
                     gwa = torch.empty((B, Otot, Ka), device=dev, dtype=torch.float32)
-                    N.call("dgv2_bmm_tn", N.ptr(gwa), N.ptr(gt3), N.ptr(h3), B, hl * wl, Ka, Otot, Otot, Ka, _dt(h),
-                           N.stream())
+                    bmm_tn_call(N.ptr(gwa), N.ptr(gt3), N.ptr(h3), B, hl * wl, Ka, Otot, Otot, Ka, _dt(h), N.stream())
                 gws = _mod_wgrad(g3, None, xs, B, H, W_, xs.shape[3], Otot, dt)   # PE columns at full resolution
                 gwb = torch.cat([gwa, gws], dim=2)
         return None, gh, None, gb, gwb, None, None, None, None, None

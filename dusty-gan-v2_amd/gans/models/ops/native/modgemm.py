@@ -354,6 +354,44 @@ if os.environ.get("DGV2_NO_PE_MID"):   # A/B switch: the round-4 routing
     _PE_FREE_MINP = {k: 4096 for k in ((64, 32), (32, 64), (128, 64), (64, 128), (32, 32), (64, 64))}
 
 
+# A/B switch: the bf16 per-sample-weight contractions of the generator's two lowest levels on gemm_stream.hip (stages of
+# four K-steps, deeper loads in flight; the same bits as the generic engines).  A module flag read at call
+# time, so that both paths can run in one process.
+_GEMM_STREAM = os.environ.get("DGV2_NO_GEMM_STREAM") is None
+# The routing is held to the geometries the kernel table was measured at (scripts/mb_gemm_lowlevels.py: the generator's
+# 4 x 32 and 8 x 64 levels, per-sample weights): maps of at most 512 pixels.  The entries themselves take more (many pixel
+# tiles, batch-shared weights: tests/test_gpu_gemm_stream.py), but nothing has shown that those shapes gain.
+_GEMM_STREAM_MAX_P = 512
+
+
+def _stream_wanted(P, per_sample=True):
+    return _GEMM_STREAM and per_sample and P <= _GEMM_STREAM_MAX_P
+
+
+def bmm_nn_sq_call(*args):
+    """dgv2_bmm_nn_sq(*args), on dgv2_gemm_stream_nn where the switch is on and the entry covers the geometry."""
+    if not (_stream_wanted(args[4], args[9] != 0) and N.try_call("dgv2_gemm_stream_nn", *args)):   # P, wstride
+        N.call("dgv2_bmm_nn_sq", *args)
+
+
+def bmm_nn_cat_sq_call(*args):
+    """dgv2_bmm_nn_cat_sq(*args), on dgv2_gemm_stream_nn_cat where the switch is on and the entry covers the geometry."""
+    if not (_stream_wanted(args[5]) and N.try_call("dgv2_gemm_stream_nn_cat", *args)):
+        N.call("dgv2_bmm_nn_cat_sq", *args)
+
+
+def bmm_tn_call(*args):
+    """dgv2_bmm_tn(*args), on dgv2_gemm_stream_tn where the switch is on and the entry covers the geometry."""
+    if not (_stream_wanted(args[4]) and N.try_call("dgv2_gemm_stream_tn", *args)):
+        N.call("dgv2_bmm_tn", *args)
+
+
+def bmm_tn_cat_call(*args):
+    """dgv2_bmm_tn_cat(*args), on dgv2_gemm_stream_tn_cat where the switch is on and the entry covers the geometry."""
+    if not (_stream_wanted(args[5]) and N.try_call("dgv2_gemm_stream_tn_cat", *args)):
+        N.call("dgv2_bmm_tn_cat", *args)
+
+
 def _bmm_nn_raw(x3, w3, out_dtype, bias=None, act=0, alpha=0.2, scale=1.0, sq=None, row_scale=None, resid=None, head=None):
     """x3 [B,P,I]; w3 [Bw,O,I] (Bw = B or 1) same dtype -> [B,P,O]; optional fused
     bias (fp32 [O]) + leaky-ReLU epilogue.  sq = _sq_args(): sum-of-squares partials where the kernel has them.
@@ -391,12 +429,15 @@ def _bmm_nn_raw(x3, w3, out_dtype, bias=None, act=0, alpha=0.2, scale=1.0, sq=No
         if resid is not None:
             resid = resid.contiguous().to(out_dtype)
             N.check(resid)
-        N.call("dgv2_bmm_nn_sq", N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I,
-               N.ptr(row_scale), N.ptr(bias), act, alpha, scale, N.ptr(resid), _dt(x3), N.dtype_code(y),
-               N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
+        bmm_nn_sq_call(N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I,
+                       N.ptr(row_scale), N.ptr(bias), act, alpha, scale, N.ptr(resid), _dt(x3), N.dtype_code(y),
+                       N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
         return y
-    N.call("dgv2_bmm_nn", N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I,
-           N.ptr(bias), act, alpha, scale, _dt(x3), N.dtype_code(y), N.stream())
+    if not (_stream_wanted(P, Bw == B) and N.try_call("dgv2_gemm_stream_nn", N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O,
+                                        0 if Bw == 1 else O * I, None, N.ptr(bias), act, alpha, scale, None, _dt(x3),
+                                        N.dtype_code(y), None, 0, None, N.stream())):
+        N.call("dgv2_bmm_nn", N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I,
+               N.ptr(bias), act, alpha, scale, _dt(x3), N.dtype_code(y), N.stream())
     return y
 
 
@@ -406,7 +447,7 @@ def _bmm_tn_raw(gy3, x3):
     I = x3.shape[2]
     N.check(gy3, x3)
     gw = torch.empty((B, O, I), device=x3.device, dtype=torch.float32)
-    N.call("dgv2_bmm_tn", N.ptr(gw), N.ptr(gy3), N.ptr(x3), B, P, I, O, O, I, _dt(x3), N.stream())
+    bmm_tn_call(N.ptr(gw), N.ptr(gy3), N.ptr(x3), B, P, I, O, O, I, _dt(x3), N.stream())
     return gw
 
 
@@ -493,8 +534,8 @@ class _ModGemmCatAct(Function):
         bias32 = bias.detach().float().contiguous()
         N.check(xa, xs, wc, bias32)
         out = torch.empty((B, H, W_, O), device=xs.device, dtype=xs.dtype)
-        N.call("dgv2_bmm_nn_cat", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wc), B, H * W_, Ka, Ks, O, N.ptr(bias32),
-               3, alpha, scale, _dt(xs), _dt(xs), N.stream())
+        bmm_nn_cat_sq_call(N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wc), B, H * W_, Ka, Ks, O, None, N.ptr(bias32),
+                           3, alpha, scale, _dt(xs), _dt(xs), None, 0, None, N.stream())
         ctx.save_for_backward(xa, xs, wc, out)
         ctx.cfg = (alpha, scale, Ka, Ks)
         return out
@@ -512,8 +553,7 @@ class _ModGemmCatAct(Function):
             gxa = _bmm_nn_raw(g3, wt, xa.dtype).reshape(xa.shape)
         if ctx.needs_input_grad[2]:
             gw = torch.empty((B, O, Ka + Ks), device=out.device, dtype=torch.float32)
-            N.call("dgv2_bmm_tn_cat", N.ptr(gw), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, H * W_, Ka, Ks, O, _dt(xs),
-                   N.stream())
+            bmm_tn_cat_call(N.ptr(gw), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, H * W_, Ka, Ks, O, _dt(xs), N.stream())
         return gxa, None, gw, gb, None, None
 
 

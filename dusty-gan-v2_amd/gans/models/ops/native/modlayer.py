@@ -90,10 +90,10 @@ class _ModLayer(Function):
                        Otot, None, N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), N.ptr(sq[0]) if sq else None,
                        _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
             else:
-                N.call("dgv2_bmm_nn_cat_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3], Otot,
-                       None, N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs),
-                       N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None,
-                       N.stream())
+                bmm_nn_cat_sq_call(N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3], Otot,
+                                   None, N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs),
+                                   N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0,
+                                   _ct.addressof(sq[1]) if sq else None, N.stream())
         else:
             xa = xa.contiguous()
             out = _bmm_nn_raw(xa.reshape(B, P, I), wb, odt, bias32, act, cfg["alpha"], cfg["scale"], sq=sq).reshape(
@@ -154,15 +154,13 @@ class _ModLayer(Function):
             pass
         elif xs is not None:
             gwb = torch.empty((B, Otot, I), device=gy.device, dtype=torch.float32)
-            N.call("dgv2_bmm_tn_cat", N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot,
-                   _dt(xs), N.stream())
+            bmm_tn_cat_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot, _dt(xs), N.stream())
         elif _TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
             # dense layers of the top levels: the streaming split-K engine of the conv weight gradient, per sample
             gwb = _bmm_tn_stream(g3, xa, B, H, W_, I, Otot)
         else:
             gwb = torch.empty((B, Otot, I), device=gy.device, dtype=torch.float32)
-            N.call("dgv2_bmm_tn", N.ptr(gwb), N.ptr(g3), N.ptr(xa.reshape(B, P, I)), B, P, I, Otot, Otot, I, _dt(xa),
-                   N.stream())
+            bmm_tn_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa.reshape(B, P, I)), B, P, I, Otot, Otot, I, _dt(xa), N.stream())
         grads = []
         off = 0
         for k in range(nm):
@@ -345,8 +343,8 @@ class _ModGemmPrepared(Function):
                 N.call("dgv2_modconv_pe_fwd_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3],
                        Otot, N.ptr(cvec), N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), *tail)
             else:
-                N.call("dgv2_bmm_nn_cat_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3], Otot,
-                       N.ptr(cvec), N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs), *tail)
+                bmm_nn_cat_sq_call(N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3], Otot,
+                                   N.ptr(cvec), N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs), *tail)
         elif pre_d is not None and not cfg["act"] and not cfg["want_sq"]:
             xa = xa.contiguous()
             if cfg.get("defer_affine"):
@@ -522,8 +520,7 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
         return torch.cat(parts, dim=2) if len(parts) > 1 else parts[0]
     if xs is not None:
         gwb = torch.empty((B, Otot, I), device=g3.device, dtype=torch.float32)
-        N.call("dgv2_bmm_tn_cat", N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot, _dt(xs),
-               N.stream())
+        bmm_tn_cat_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot, _dt(xs), N.stream())
         return gwb
     if _TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
         return _bmm_tn_stream(g3, xa, B, H, W_, I, Otot)
@@ -532,7 +529,7 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
         if gwb is not None:
             return gwb
     gwb = torch.empty((B, Otot, I), device=g3.device, dtype=torch.float32)
-    N.call("dgv2_bmm_tn", N.ptr(gwb), N.ptr(g3), N.ptr(xa.reshape(B, P, I)), B, P, I, Otot, Otot, I, _dt(xa), N.stream())
+    bmm_tn_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa.reshape(B, P, I)), B, P, I, Otot, Otot, I, _dt(xa), N.stream())
     return gwb
 
 

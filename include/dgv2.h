@@ -696,6 +696,34 @@ int dgv2_conv1x1_fwd(void* y, const void* x, const void* wf, int B, int P, int C
 int dgv2_conv1x1_dgrad(void* gx, const void* gy, const void* wt, int B, int P, int C, int O, const void* resid,
                        int dtype, void* stream);
 
+/* The bf16 per-sample-weight contractions of the generator's two lowest levels with a deeper operand delivery
+ * (gemm_stream.hip: stages of four K-steps per barrier, the next stage's loads in flight across the MFMAs, the pixel
+ * operand of the NN form straight from global memory into the matrix cores, the fp32 tile of the TN form in 16-byte
+ * stores).  Arguments and RESULTS are those of the generic entries, bit for bit -- every output, every sum-of-squares
+ * partial and the slot it is written to (same block tile, same fragment ownership, the K-steps of 32 ascending into one
+ * accumulator per fragment, the same epilogue):
+ *   dgv2_gemm_stream_nn      = dgv2_bmm_nn_sq       dgv2_gemm_stream_nn_cat = dgv2_bmm_nn_cat_sq
+ *   dgv2_gemm_stream_tn      = dgv2_bmm_tn          dgv2_gemm_stream_tn_cat = dgv2_bmm_tn_cat
+ * Invalid arguments: DGV2_EINVAL as the generic entry.  DGV2_ENOTSUP (nothing launched; callers run the generic entry)
+ * outside:  NN: DGV2_BF16 in and out, O > 64 (the generic 128-channel tile), contraction length a multiple of 32 (cat:
+ * Ka % 32 == 0 and Ks % 32 == 0), ldx % 8 == 0, wstride % 8 == 0, ldy % 4 == 0, 16-byte aligned y / x / w / resid, one
+ * sample's operand below 2^31 elements;  TN: DGV2_BF16, O > 32 and O % 8 == 0 (the generic 64 x 128 tile), no split-K
+ * (B * ceil(O / 64) * ceil(J / 128) >= 512 or P < 1024), I % 8 == 0, ldgy % 8 == 0, ldx % 8 == 0, 16-byte aligned
+ * gw / gy / x.
+ * replaces: nothing new -- another engine for the grouped F.conv2d of ModConv2d.forward and its gradients
+ *   (gans/models/ops/style.py:105-118) at the 4 x 32 and 8 x 64 levels of the generator (gans/models/dusty_v2.py:153-170). */
+int dgv2_gemm_stream_nn(void* y, const void* x, const void* w, int B, int P, int I, int O, int ldx, int ldy,
+                        int64_t wstride, const float* row_scale, const float* bias, int act, float alpha, float scale,
+                        const void* resid, int dtype, int ydtype, float* sumsq, int sumsq_cap, int* sumsq_used,
+                        void* stream);
+int dgv2_gemm_stream_nn_cat(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka, int Ks, int O,
+                            const float* row_scale, const float* bias, int act, float alpha, float scale, int dtype,
+                            int ydtype, float* sumsq, int sumsq_cap, int* sumsq_used, void* stream);
+int dgv2_gemm_stream_tn(float* gw, const void* gy, const void* x, int B, int P, int I, int O, int ldgy, int ldx, int dtype,
+                        void* stream);
+int dgv2_gemm_stream_tn_cat(float* gw, const void* gy, const void* xa, const void* xs, int B, int P, int Ka, int Ks, int O,
+                            int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------
  * discriminator stem in one pass: BlurVH -> 1x1 conv (2 -> O) -> bias + leaky ReLU, and its backward.
  * replaces: Discriminator layers[0:3] (dusty_v2.py:364-367) = ops.BlurVH (common.py:141-155) +
