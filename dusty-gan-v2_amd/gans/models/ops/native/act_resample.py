@@ -263,6 +263,12 @@ def _sq_args(dev):
     return torch.empty(_SQ_CAP, device=dev, dtype=torch.float32), _ct.c_int(0)
 
 
+def _sq_partials(sq, out):
+    """The partial sums of squares of out: what the producing kernel left in sq = _sq_args(), or -- sq None, or a kernel
+    without that epilogue -- a pass of their own over out."""
+    return sq[0][:sq[1].value] if (sq is not None and sq[1].value > 0) else sum_squares(out)
+
+
 def _resample_raw(x, spec, adjoint, in_hw, out=None, ldy=None, ldx=None, C=None, sq=None):
     """x [B,h,w,ldx]; forward maps in_hw -> spec.out_size(in_hw); adjoint the other way.
     sq = _sq_args(): also leave the sum-of-squares partials of the output (sq[1].value of them, 0 = unsupported)."""
@@ -305,7 +311,7 @@ class _ResampleSq(Function):
         ctx.cfg = (spec, in_hw)
         sq = _sq_args(x.device)
         y = _resample_raw(x, spec, False, in_hw, sq=sq)
-        part = sq[0][:sq[1].value] if sq[1].value > 0 else sum_squares(y)
+        part = _sq_partials(sq, y)
         ctx.mark_non_differentiable(part)
         return y, part
 

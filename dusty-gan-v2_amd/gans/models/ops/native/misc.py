@@ -364,7 +364,7 @@ class _ModUpPrepared(Function):
         ctx.cfg = dict(cfg, has_bias=bias is not None)
         ctx.save_for_backward(h, xs, wb, out if cfg["act"] else None, cvec, wt)
         if cfg["want_sq"]:
-            part = sq[0][:sq[1].value] if (sq is not None and sq[1].value > 0) else sum_squares(out)
+            part = _sq_partials(sq, out)
             ctx.mark_non_differentiable(part)
             return out, part
         return out
@@ -383,37 +383,7 @@ class _ModUpPrepared(Function):
         hl, wl, Ka = h.shape[1:]
         P = H * W_
         dev = gy.device
-        # accumulator gradient (c[o] applied) and bias gradient: the activation backward of _ModGemmPrepared
-        gb = None
-        vn = 8 if gy.dtype == torch.bfloat16 else 4
-        rows = gy.numel() // Otot
-        link = cfg.get("defer")
-        if link is not None and bool(link.get("done")):
-            # the layer that consumed this output (conv2 of the level) already ran THIS layer's activation backward in
-            # the epilogue of its data-gradient kernel (modlayer._dgrad_actbwd): gy is the accumulator gradient, the
-            # bias gradient waits in `link`
-            gpre, gb = gy.to(dt), (link.get("gb") if cfg["has_bias"] else None)
-            link.clear()
-        elif cfg["act"] and gy.dtype == dt and Otot % vn == 0 and 256 % (Otot // vn) == 0:
-            gpre = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
-            gb = torch.empty(Otot, device=dev, dtype=torch.float32)
-            # partial column sums + fold kernel at every size: the bias gradient is the same bits every run
-            scratch = torch.empty(2048 * Otot, device=dev, dtype=torch.float32)
-            N.call("dgv2_bias_act_bwd_rs", N.ptr(gpre), N.ptr(gb), N.ptr(gy), N.ptr(out), rows, Otot, cfg["alpha"],
-                   cfg["scale"], N.ptr(cvec), N.ptr(scratch), scratch.numel(), _dt(gy),
-                   N.stream())
-            if not cfg["has_bias"]:
-                gb = None
-        else:
-            gpre = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
-            g0 = gy
-            if cfg["act"]:
-                g0 = _bias_act_raw(gy, None, out, 1, cfg["alpha"], cfg["scale"], 1, Otot)
-            if cfg["has_bias"]:
-                gb = torch.empty(Otot, device=dev, dtype=torch.float32)
-                N.call("dgv2_bias_grad", N.ptr(gb), N.ptr(g0), g0.numel(), 1, Otot, _dt(g0), N.stream())
-            N.call("dgv2_scale_cast", N.ptr(gpre), N.ptr(g0), N.ptr(cvec), g0.numel(), Otot, _dt(g0), _dt(gpre),
-                   N.stream())
+        gpre, gb = _mod_act_bwd(cfg, gy, out, cvec, dt)
         g3 = gpre.reshape(B, P, Otot)
         need_h, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
         gh = gwb = None
@@ -456,28 +426,6 @@ def mod_up_layer(h, xs, spec, handle, wb, cvec, bias=None, act=True, alpha=0.2, 
                defer=defer)   # defer: see mod_gemm_layer
     t, wimg = (None, None) if pre is None else pre[:2]
     return _ModUpPrepared.apply(cfg, h, xs, bias, handle, wb, cvec, wt, t, wimg)
-
-
-def mod_gemm_layer(xa, xs, handle, wb, cvec, bias=None, act=True, alpha=0.2, scale=math.sqrt(2.0), out_dtype=None,
-                   want_sq=False, wt=None, fork=False, defer=None, upstream=None, head_w=None, pre_d=None,
-                   defer_affine=False):
-    """defer: a dict shared with the ONE consumer of this layer's output (a head in fork form); when that consumer
-    ran this layer's activation backward inside its own data-gradient kernel it marks the dict and this layer's
-    backward skips its own pass.  upstream: the consumer's side of the same link (see _head_dgrad_actbwd).
-    The contraction of a modulated layer whose weights came from mod_prep_all (handle, wb) and whose
-    input-magnitude factor is cvec fp32 [Otot] (native.ema_update(..., cvec=...)).
-    head_w: also return (behind the output and its statistic) the contraction of the level's two output heads on this
-    layer's output where the kernel takes it in its epilogue (an empty tensor where it does not);
-    pre_d: this layer is the heads and that contraction exists already (see _ModGemmPrepared.forward)."""
-    ref = xa if xa is not None else xs
-    cfg = dict(act=bool(act), alpha=float(alpha), scale=float(scale) if act else 1.0,
-               out_dtype=ref.dtype if out_dtype is None else out_dtype, want_sq=bool(want_sq),
-               fork=bool(fork and xa is not None and xa.requires_grad), defer=defer, upstream=upstream,
-               defer_affine=bool(defer_affine))
-    if pre_d is not None and pre_d.numel() == 0:
-        pre_d = None
-    return _ModGemmPrepared.apply(cfg, xa, xs, bias, handle, wb, cvec, wt, head_w, pre_d)
-
 
 
 __all__ = [n_ for n_ in dir() if not n_.startswith("__")]

@@ -39,6 +39,22 @@ def _bmm_tn_stream(g3, xa, B, H, W_, I, O, shared=False, out=None):
     return gw
 
 
+def _pe_cat_fwd(out, xa, xs, wb, cvec, bias32, act, cfg, sq):
+    """out [B,H,W,Otot] = act(c[o] * ([xa | xs] . wb[b,o,:]) + bias[o]) on the batch-shared PE xs [1,H,W,Ks]; xa
+    [B,H,W,Ka] or None, cvec fp32 [Otot] or None (c = 1), sq = _sq_args() or None."""
+    B, H, W_, Otot = out.shape
+    Ka = 0 if xa is None else xa.shape[3]
+    Ks = xs.shape[3]
+    tail = (N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
+    if _PE_FWD and out.dtype == torch.bfloat16 and (Ka, Ks, Otot) in ((64, 512, 32), (128, 512, 64), (256, 512, 128)):
+        # top pyramid levels: pixel-tile blocks walking the samples, PE fragments in registers
+        N.call("dgv2_modconv_pe_fwd_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, H * W_, Ka, Ks, Otot, N.ptr(cvec),
+               N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), *tail)
+    else:
+        bmm_nn_cat_sq_call(N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, H * W_, Ka, Ks, Otot, N.ptr(cvec),
+                           N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs), *tail)
+
+
 class _ModLayer(Function):
     @staticmethod
     def forward(ctx, cfg, xa, xs, bias, shift, fw, *mods):
@@ -81,19 +97,9 @@ class _ModLayer(Function):
         if xs is not None:
             xs = xs.contiguous()
             xa = None if xa is None else xa.contiguous()
-            Ka = 0 if xa is None else xa.shape[3]
             out = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
             N.check(xa, xs, wb, bias32)
-            if _PE_FWD and dt == torch.bfloat16 and (Ka, xs.shape[3], Otot) in ((64, 512, 32), (128, 512, 64), (256, 512, 128)):
-                # top pyramid levels: pixel-tile blocks walking the samples, PE fragments in registers
-                N.call("dgv2_modconv_pe_fwd_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3],
-                       Otot, None, N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), N.ptr(sq[0]) if sq else None,
-                       _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
-            else:
-                bmm_nn_cat_sq_call(N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3], Otot,
-                                   None, N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs),
-                                   N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0,
-                                   _ct.addressof(sq[1]) if sq else None, N.stream())
+            _pe_cat_fwd(out, xa, xs, wb, None, bias32, act, cfg, sq)
         else:
             xa = xa.contiguous()
             out = _bmm_nn_raw(xa.reshape(B, P, I), wb, odt, bias32, act, cfg["alpha"], cfg["scale"], sq=sq).reshape(
@@ -101,7 +107,7 @@ class _ModLayer(Function):
         ctx.cfg = dict(cfg, Os=Os, I=I, B=B, rot=rot, has_bias=bias is not None)
         ctx.save_for_backward(xa, xs, wb, out if cfg["act"] else None, shift, fw, *Ws, *Ss, *Es, *saved_small)
         if cfg["want_sq"]:
-            part = sq[0][:sq[1].value] if (sq is not None and sq[1].value > 0) else sum_squares(out)
+            part = _sq_partials(sq, out)
             ctx.mark_non_differentiable(part)
             return out, part
         return out
@@ -136,31 +142,7 @@ class _ModLayer(Function):
         if xa is not None and ctx.needs_input_grad[1]:
             wt = wb[:, :, :Ka].transpose(1, 2).contiguous()
             gxa = _bmm_nn_raw(g3, wt, xa.dtype).reshape(xa.shape)
-        gwb = None
-        if xs is not None and _LIB_WGRAD and dt == torch.bfloat16 and P >= 2048:
-            # plain batched GEMMs (K = pixels of one sample, fp32 out): hipBLASLt's split-K kernels beat the
-            # generic dgv2 TN kernel on these long-K / short-M shapes; the batch-shared PE is a stride-0 operand
-            gT = g3.transpose(1, 2)
-            parts = []
-            if xa is not None and _TN_STREAM and Ka % 8 == 0 and Otot % 8 == 0:
-                parts.append(_bmm_tn_stream(g3, xa, B, H, W_, Ka, Otot))   # own streaming engine, per sample
-            elif xa is not None:
-                parts.append(torch.bmm(gT, xa.reshape(B, P, Ka), out_dtype=torch.float32))
-            gws = pe_wgrad(g3, xs.reshape(P, -1))   # several samples share a staged PE tile (csrc/pe_wgrad.hip)
-            parts.append(gws if gws is not None else
-                         torch.bmm(gT, xs.reshape(1, P, -1).expand(B, P, xs.shape[3]), out_dtype=torch.float32))
-            gwb = torch.cat(parts, dim=2) if len(parts) > 1 else parts[0]
-        if gwb is not None:
-            pass
-        elif xs is not None:
-            gwb = torch.empty((B, Otot, I), device=gy.device, dtype=torch.float32)
-            bmm_tn_cat_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot, _dt(xs), N.stream())
-        elif _TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
-            # dense layers of the top levels: the streaming split-K engine of the conv weight gradient, per sample
-            gwb = _bmm_tn_stream(g3, xa, B, H, W_, I, Otot)
-        else:
-            gwb = torch.empty((B, Otot, I), device=gy.device, dtype=torch.float32)
-            bmm_tn_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa.reshape(B, P, I)), B, P, I, Otot, Otot, I, _dt(xa), N.stream())
+        gwb = _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt)
         grads = []
         off = 0
         for k in range(nm):
@@ -311,6 +293,48 @@ def mod_prep_all(layers, groups, shift):
     return list(zip(out[:ng], out[ng:2 * ng], wts))
 
 
+def _link_mark(up, gb):
+    """The writing side of a link (the plain dict a layer and the ONE consumer of its output share as defer= /
+    upstream=dict(link=...)): the consumer's data-gradient kernel ran the upstream layer's activation backward and
+    leaves that layer's bias gradient gb fp32 [K]; _mod_act_bwd is the reading side."""
+    up["link"]["done"] = True
+    up["link"]["gb"] = gb
+
+
+def _mod_act_bwd(cfg, gy, out, cvec, dt):
+    """Activation backward of a prepared layer y = act(c[o] * acc + bias[o]): gy [B,H,W,Otot] -> (gradient of the
+    accumulator in dt, c[o] applied; bias gradient fp32 [Otot] or None, which sums the unscaled one)."""
+    Otot = gy.shape[3]
+    link = cfg.get("defer")
+    if link is not None and bool(link.get("done")):
+        # the layer that consumed this output (a head in fork form, conv2 of the level) already ran THIS layer's
+        # activation backward in the epilogue of its data-gradient kernel: gy is the accumulator gradient, the bias
+        # gradient waits in `link`
+        gpre, gb = gy.to(dt), (link.get("gb") if cfg["has_bias"] else None)
+        link.clear()
+        return gpre, gb
+    gpre = torch.empty(gy.shape, device=gy.device, dtype=dt)
+    gb = None
+    vn = 8 if gy.dtype == torch.bfloat16 else 4
+    if cfg["act"] and gy.dtype == dt and Otot % vn == 0 and 256 % (Otot // vn) == 0:
+        gb = torch.empty(Otot, device=gy.device, dtype=torch.float32)
+        # partial column sums + fold kernel at every size: the bias gradient is the same bits every run
+        scratch = torch.empty(2048 * Otot, device=gy.device, dtype=torch.float32)
+        N.call("dgv2_bias_act_bwd_rs", N.ptr(gpre), N.ptr(gb), N.ptr(gy), N.ptr(out), gy.numel() // Otot, Otot,
+               cfg["alpha"], cfg["scale"], N.ptr(cvec), N.ptr(scratch), scratch.numel(), _dt(gy), N.stream())
+        if not cfg["has_bias"]:
+            gb = None
+    else:
+        g0 = gy
+        if cfg["act"]:
+            g0 = _bias_act_raw(gy, None, out, 1, cfg["alpha"], cfg["scale"], 1, Otot)
+        if cfg["has_bias"]:
+            gb = torch.empty(Otot, device=gy.device, dtype=torch.float32)
+            N.call("dgv2_bias_grad", N.ptr(gb), N.ptr(g0), g0.numel(), 1, Otot, _dt(g0), N.stream())
+        N.call("dgv2_scale_cast", N.ptr(gpre), N.ptr(g0), N.ptr(cvec), g0.numel(), Otot, _dt(g0), _dt(gpre), N.stream())
+    return gpre, gb
+
+
 class _ModGemmPrepared(Function):
     """y = act(c[o] * ([xa | xs] . wb[b,o,:]) + bias[o]) with weights prepared by mod_prep_all; `handle` carries
     the gradient dL/dwb back to the batched preparation, c (fp32 [Otot], no gradient) is the layers' output factor."""
@@ -336,15 +360,8 @@ class _ModGemmPrepared(Function):
         if xs is not None:
             xs = xs.contiguous()
             xa = None if xa is None else xa.contiguous()
-            Ka = 0 if xa is None else xa.shape[3]
             out = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
-            tail = (N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
-            if _PE_FWD and dt == torch.bfloat16 and (Ka, xs.shape[3], Otot) in ((64, 512, 32), (128, 512, 64), (256, 512, 128)):
-                N.call("dgv2_modconv_pe_fwd_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3],
-                       Otot, N.ptr(cvec), N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), *tail)
-            else:
-                bmm_nn_cat_sq_call(N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, P, Ka, xs.shape[3], Otot,
-                                   N.ptr(cvec), N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), _dt(xs), *tail)
+            _pe_cat_fwd(out, xa, xs, wb, cvec, bias32, act, cfg, sq)
         elif pre_d is not None and not cfg["act"] and not cfg["want_sq"]:
             xa = xa.contiguous()
             if cfg.get("defer_affine"):
@@ -363,7 +380,7 @@ class _ModGemmPrepared(Function):
         ctx.save_for_backward(xa, xs, wb, out if cfg["act"] else None, cvec, wt)
         outs = [out]
         if cfg["want_sq"]:
-            part = sq[0][:sq[1].value] if (sq is not None and sq[1].value > 0) else sum_squares(out)
+            part = _sq_partials(sq, out)
             ctx.mark_non_differentiable(part)
             outs.append(part)
         if head_w is not None:
@@ -395,40 +412,7 @@ class _ModGemmPrepared(Function):
                 return None, gxa, None, (gbh if cfg["has_bias"] else None), gwb, None, None, None, None, None
         H, W_ = gy.shape[1:3]
         P = H * W_
-        dev = gy.device
-        # gradient w.r.t. the accumulator (c[o] applied; the bias gradient sums the unscaled one)
-        gb = None
-        vn = 8 if gy.dtype == torch.bfloat16 else 4
-        rows = gy.numel() // Otot
-        link = cfg.get("defer")
-        deferred = link is not None and bool(link.get("done"))
-        if deferred:
-            # the layer that consumed this output (a head, fork form) already ran THIS layer's activation backward in
-            # the epilogue of its data-gradient kernel: gy is the accumulator gradient, the bias gradient waits in `link`
-            gpre, gb = gy.to(dt), (link.get("gb") if cfg["has_bias"] else None)
-            link.clear()
-        else:
-            gpre = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
-        if deferred:
-            pass
-        elif cfg["act"] and gy.dtype == dt and Otot % vn == 0 and 256 % (Otot // vn) == 0:
-            gb = torch.empty(Otot, device=dev, dtype=torch.float32)
-            # partial column sums + fold kernel at every size: the bias gradient is the same bits every run
-            scratch = torch.empty(2048 * Otot, device=dev, dtype=torch.float32)
-            N.call("dgv2_bias_act_bwd_rs", N.ptr(gpre), N.ptr(gb), N.ptr(gy), N.ptr(out), rows, Otot, cfg["alpha"],
-                   cfg["scale"], N.ptr(cvec), N.ptr(scratch), scratch.numel(), _dt(gy),
-                   N.stream())
-            if not cfg["has_bias"]:
-                gb = None
-        else:
-            g0 = gy
-            if cfg["act"]:
-                g0 = _bias_act_raw(gy, None, out, 1, cfg["alpha"], cfg["scale"], 1, Otot)
-            if cfg["has_bias"]:
-                gb = torch.empty(Otot, device=dev, dtype=torch.float32)
-                N.call("dgv2_bias_grad", N.ptr(gb), N.ptr(g0), g0.numel(), 1, Otot, _dt(g0), N.stream())
-            N.call("dgv2_scale_cast", N.ptr(gpre), N.ptr(g0), N.ptr(cvec), g0.numel(), Otot, _dt(g0), _dt(gpre),
-                   N.stream())
+        gpre, gb = _mod_act_bwd(cfg, gy, out, cvec, dt)
         g3 = gpre.reshape(B, P, Otot)
         Ka = 0 if xa is None else xa.shape[3]
         gxa = None
@@ -454,12 +438,25 @@ class _ModGemmPrepared(Function):
         return None, gxa, None, gb, gwb, None, None, None, None, None
 
 
-# the positional-encoding part on the own streaming engine (shared-x mode): measured SLOWER than the library's batched
-# GEMM on every level (3996 vs 4031 img/s), so it is opt-in for experiments only
-_PE_TN_STREAM = os.environ.get("DGV2_PE_TN_STREAM") is not None
-
-
-_PE_TN_MINP = int(os.environ.get("DGV2_PE_TN_MINP", "16384"))
+def mod_gemm_layer(xa, xs, handle, wb, cvec, bias=None, act=True, alpha=0.2, scale=math.sqrt(2.0), out_dtype=None,
+                   want_sq=False, wt=None, fork=False, defer=None, upstream=None, head_w=None, pre_d=None,
+                   defer_affine=False):
+    """defer: a dict shared with the ONE consumer of this layer's output (a head in fork form); when that consumer
+    ran this layer's activation backward inside its own data-gradient kernel it marks the dict and this layer's
+    backward skips its own pass.  upstream: the consumer's side of the same link (see _head_dgrad_actbwd).
+    The contraction of a modulated layer whose weights came from mod_prep_all (handle, wb) and whose
+    input-magnitude factor is cvec fp32 [Otot] (native.ema_update(..., cvec=...)).
+    head_w: also return (behind the output and its statistic) the contraction of the level's two output heads on this
+    layer's output where the kernel takes it in its epilogue (an empty tensor where it does not);
+    pre_d: this layer is the heads and that contraction exists already (see _ModGemmPrepared.forward)."""
+    ref = xa if xa is not None else xs
+    cfg = dict(act=bool(act), alpha=float(alpha), scale=float(scale) if act else 1.0,
+               out_dtype=ref.dtype if out_dtype is None else out_dtype, want_sq=bool(want_sq),
+               fork=bool(fork and xa is not None and xa.requires_grad), defer=defer, upstream=upstream,
+               defer_affine=bool(defer_affine))
+    if pre_d is not None and pre_d.numel() == 0:
+        pre_d = None
+    return _ModGemmPrepared.apply(cfg, xa, xs, bias, handle, wb, cvec, wt, head_w, pre_d)
 
 
 _PE_WGRAD = os.environ.get("DGV2_NO_PE_WGRAD") is None   # A/B switch for benchmarking
@@ -493,7 +490,8 @@ def pe_wgrad(g3, xs, out=None, col0=0):
 
 
 def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
-    """gwb fp32 [B,Otot,I] = per-sample g3^T [xa | xs] (the engine choice of _ModLayer.backward)."""
+    """gwb fp32 [B,Otot,I] = per-sample g3^T [xa | xs].  The single place where the weight-gradient engine of a modulated
+    layer is chosen: _ModLayer, _ModGemmPrepared and the full-resolution PE columns of _ModUpPrepared all come here."""
     P = H * W_
     Ka = 0 if xa is None else xa.shape[3]
     if (xs is not None and xa is not None and _LIB_WGRAD and dt == torch.bfloat16 and P >= 2048 and _TN_STREAM and Ka % 8 == 0
@@ -504,25 +502,24 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
             _bmm_tn_stream(g3, xa, B, H, W_, Ka, Otot, out=gwb)
             return gwb
     if xs is not None and _LIB_WGRAD and dt == torch.bfloat16 and P >= 2048:
+        # plain batched GEMMs (K = pixels of one sample, fp32 out): hipBLASLt's split-K kernels beat the
+        # generic dgv2 TN kernel on these long-K / short-M shapes; the batch-shared PE is a stride-0 operand
         gT = g3.transpose(1, 2)
         parts = []
         if xa is not None and _TN_STREAM and Ka % 8 == 0 and Otot % 8 == 0:
-            parts.append(_bmm_tn_stream(g3, xa, B, H, W_, Ka, Otot))
+            parts.append(_bmm_tn_stream(g3, xa, B, H, W_, Ka, Otot))   # own streaming engine, per sample
         elif xa is not None:
             parts.append(torch.bmm(gT, xa.reshape(B, P, Ka), out_dtype=torch.float32))
-        gws = pe_wgrad(g3, xs.reshape(P, -1))
-        if gws is not None:
-            parts.append(gws)
-        elif _PE_TN_STREAM and Otot % 8 == 0 and P >= _PE_TN_MINP:
-            parts.append(_bmm_tn_stream(g3, xs.contiguous(), B, H, W_, xs.shape[3], Otot, shared=True))
-        else:
-            parts.append(torch.bmm(gT, xs.reshape(1, P, -1).expand(B, P, xs.shape[3]), out_dtype=torch.float32))
+        gws = pe_wgrad(g3, xs.reshape(P, -1))   # several samples share a staged PE tile (csrc/pe_wgrad.hip)
+        parts.append(gws if gws is not None else
+                     torch.bmm(gT, xs.reshape(1, P, -1).expand(B, P, xs.shape[3]), out_dtype=torch.float32))
         return torch.cat(parts, dim=2) if len(parts) > 1 else parts[0]
     if xs is not None:
         gwb = torch.empty((B, Otot, I), device=g3.device, dtype=torch.float32)
         bmm_tn_cat_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot, _dt(xs), N.stream())
         return gwb
     if _TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
+        # dense layers of the top levels: the streaming split-K engine of the conv weight gradient, per sample
         return _bmm_tn_stream(g3, xa, B, H, W_, I, Otot)
     if Otot <= 4 and g3.dtype == xa.dtype:
         gwb = _bmm_tn_small(g3, xa, B, P, I, Otot)   # the output heads: streaming weighted column sum
@@ -572,8 +569,7 @@ def _dgrad_actbwd(g3, wt, xa, up):
     if not N.try_call("dgv2_modconv_pe_dgrad_actbwd", N.ptr(gpre), N.ptr(gb), N.ptr(scratch), scratch.numel(), None, N.ptr(g3),
                       N.ptr(wt), N.ptr(xr), N.ptr(up["cvec"]), up["alpha"], up["scale"], B, P, K, N.BF16, N.stream()):
         return None
-    up["link"]["done"] = True
-    up["link"]["gb"] = gb
+    _link_mark(up, gb)
     return gpre
 
 
@@ -602,8 +598,7 @@ def _head_dgrad_actbwd(g3, wt, resid, xa, up):
     N.check(g3, wt, r, xr, up["cvec"])
     N.call("dgv2_bmm_nn_small_act", N.ptr(y), N.ptr(g3), N.ptr(wt), N.ptr(r), B, P, Otot, Ka, N.ptr(xr), N.ptr(up["cvec"]),
            up["alpha"], up["scale"], N.ptr(gb), N.ptr(scratch), scratch.numel(), None, _dt(xa), N.stream())
-    up["link"]["done"] = True
-    up["link"]["gb"] = gb
+    _link_mark(up, gb)
     return y
 
 _HEAD_BWD = os.environ.get("DGV2_NO_HEAD_BWD") is None   # A/B switch for benchmarking
@@ -638,8 +633,7 @@ def _head_bwd_fused(gy, cvec, wt, resid, xa, up):
                       N.ptr(gy), N.ptr(cvec), N.ptr(wt), N.ptr(r), N.ptr(xr), N.ptr(up["cvec"]), up["alpha"], up["scale"],
                       B, P, Otot, Ka, _dt(xa), N.stream()):
         return None
-    up["link"]["done"] = True
-    up["link"]["gb"] = gb_up
+    _link_mark(up, gb_up)
     return y, gwb, gbh
 
 

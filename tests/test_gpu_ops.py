@@ -369,6 +369,92 @@ def test_batched_weight_preparation_matches_per_layer_path(nat, dtype, tol):
         assert_rel(gg.float().cpu(), gr.float().cpu(), tol * 5, name)
 
 
+@pytest.mark.parametrize("has_bias", [True, False])
+@pytest.mark.parametrize("Otot,route", [(32, "dgv2_bias_act_bwd_rs"), (24, "dgv2_scale_cast")])
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 2e-2)])
+def test_shared_activation_backward_of_the_prepared_layers_against_float64(nat, monkeypatch, dtype, tol, Otot, route, has_bias):
+    """native._mod_act_bwd, the one activation backward of _ModGemmPrepared and _ModUpPrepared, against the float64
+    statement gpre = c[o] * gy * (out > 0 ? 1 : alpha) * scale, gb = sum over rows of gy * (...) * scale
+    (FusedLeakyReLU backward, fused_act.py:46-59, with the input-magnitude factor of style.py:105-118).  Otot = 32 takes
+    the one-launch route (dgv2_bias_act_bwd_rs), Otot = 24 the composed one (24 / 8 = 3 and 24 / 4 = 6 do not divide
+    256); the third route -- a link the consumer marked -- launches nothing and hands back the link's bias gradient."""
+    import dgv2_native as N
+    g = torch.Generator().manual_seed(3 * Otot + int(has_bias))
+    B, H, W = 2, 2, 8
+    alpha, scale = 0.2, math.sqrt(2.0)
+    gy = torch.randn(B, H, W, Otot, generator=g).to(DEV).to(dtype)
+    out = torch.randn(B, H, W, Otot, generator=g).to(DEV).to(dtype)
+    out[0, 0, :3, :5] = 0.0                                   # exact zeros take the negative branch (out > 0 is false)
+    cvec = (torch.rand(Otot, generator=g) + 0.5).to(DEV)
+    names = []
+    inner = N.call
+    monkeypatch.setattr(N, "call", lambda name, *a: (names.append(name), inner(name, *a))[1])
+    cfg = dict(act=True, alpha=alpha, scale=scale, has_bias=has_bias, defer=None)
+    gpre, gb = nat._mod_act_bwd(cfg, gy, out, cvec, dtype)
+    assert route in names and ("dgv2_bias_act_bwd_rs" in names) == (Otot == 32), names
+    g0 = gy.double() * torch.where(out > 0, 1.0, alpha).double() * scale
+    assert gpre.dtype == dtype and gpre.shape == gy.shape
+    assert_rel(gpre.double().cpu(), (g0 * cvec.double()).cpu(), tol, "gpre")
+    if has_bias:
+        assert gb.dtype == torch.float32
+        assert_rel(gb.double().cpu(), g0.sum((0, 1, 2)).cpu(), 5 * tol, "gb")
+    else:
+        assert gb is None
+    # a link marked done: gy IS the accumulator gradient
+    del names[:]
+    marker = torch.full((Otot,), 7.0, device=DEV)
+    link = dict(done=True, gb=marker)
+    gpre, gb = nat._mod_act_bwd(dict(cfg, defer=link), gy.float(), out, cvec, dtype)
+    assert torch.equal(gpre, gy.float().to(dtype)) and gpre.dtype == dtype and not names
+    assert (gb is marker) if has_bias else (gb is None)
+    assert link == {}
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 2e-2)])
+def test_heads_layer_takes_one_weight_gradient_engine_through_both_nodes(nat, monkeypatch, dtype, tol):
+    """The heads' layer (Otot = 3 = 1 + 2, I = 24, no demodulation, no activation, fp32 output) through the per-layer node
+    (mod_layer) and through mod_prep_all + mod_gemm_layer with the same W, s and ema_var: both nodes take their weight
+    gradient from native._mod_wgrad, and every gradient agrees within the bounds of
+    test_batched_weight_preparation_matches_per_layer_path."""
+    from gans.models.ops.native import modlayer
+    g = torch.Generator().manual_seed(43)
+    B, H, W, I = 2, 4, 16, 24
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(DEV)
+
+    Ws = [rnd(1, I).requires_grad_(True), rnd(2, I).requires_grad_(True)]
+    Ss = [rnd(B, I, scale=0.5).requires_grad_(True) for _ in range(2)]
+    evs = [torch.tensor([v], device=DEV) for v in (0.4, 2.5)]
+    x = rnd(B, H, W, I).to(dtype).requires_grad_(True)
+    bias = rnd(3).requires_grad_(True)
+    gy = rnd(B, H, W, 3)
+    leaves = [*Ws, *Ss, x, bias]
+    calls = []
+    inner = modlayer._mod_wgrad
+
+    def spy(g3, xa, xs, *a):
+        calls.append((tuple(g3.shape), xs is None))
+        return inner(g3, xa, xs, *a)
+
+    monkeypatch.setattr(modlayer, "_mod_wgrad", spy)
+    y = nat.mod_layer(x, None, [(Ws[0], Ss[0], evs[0], False), (Ws[1], Ss[1], evs[1], False)], bias=bias, act=False,
+                      out_dtype=torch.float32)
+    want = torch.autograd.grad(y, leaves, gy)
+    assert calls == [((B, H * W, 3), True)]
+    layers = [dict(W=Ws[0], s=Ss[0], O=1, I=I, demod=False, cin=0, fw=None, group=0, row_off=0),
+              dict(W=Ws[1], s=Ss[1], O=2, I=I, demod=False, cin=0, fw=None, group=0, row_off=1)]
+    handle, wb, wt = nat.mod_prep_all(layers, [dict(Otot=3, I=I, dtype=dtype)], None)[0]
+    cvec = torch.cat([(1.0 / (torch.sqrt(e) + 1e-8)).expand(n) for e, n in zip(evs, (1, 2))]).contiguous()
+    z = nat.mod_gemm_layer(x, None, handle, wb, cvec, bias=bias, act=False, out_dtype=torch.float32)
+    got = torch.autograd.grad(z, leaves, gy)
+    assert calls == [((B, H * W, 3), True)] * 2
+    assert y.dtype == z.dtype == torch.float32
+    assert_rel(z.detach().cpu(), y.detach().cpu(), tol, "heads")
+    for a, b, name in zip(got, want, ("gW0", "gW1", "gs0", "gs1", "gx", "gb")):
+        assert_rel(a.float().cpu(), b.float().cpu(), tol * 5, name)
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-5), (torch.bfloat16, 8e-3)])
 @pytest.mark.parametrize("B,splits,group", [(8, 1, 4), (16, 2, 4), (6, 2, 4), (4, 1, 4)])
 def test_mbstd_cat_matches_composed_reference(nat, dtype, tol, B, splits, group):
@@ -2090,6 +2176,72 @@ def test_dgrad_with_upstream_activation_backward_is_bit_identical_to_the_two_lau
     assert got is not None and link.get("done") is True
     assert torch.equal(got.view(torch.int16), want.view(torch.int16))
     assert_rel(link["gb"].cpu(), want_b.cpu(), 1e-5, "bias gradient")
+
+
+@pytest.mark.parametrize("conv1", ["cat", "up"])
+def test_link_between_the_prepared_nodes_gives_the_bits_of_the_separate_activation_backward(nat, monkeypatch, conv1):
+    """conv1 -> conv2 of a generator level as autograd nodes (weights from mod_prep_all), conv1 either on the materialised
+    up2(h) (mod_gemm_layer) or in the commuted form (mod_up_layer), sharing a link with conv2: with conv1's activation
+    backward taken in the epilogue of conv2's data gradient (_dgrad_actbwd marks the link, conv1's node reads it) every
+    gradient has the bits of the run in which conv1's node does that pass itself -- except conv1's bias gradient, which
+    agrees to summation order.  B = 2, K = O = 32 at 16 x 256 pixels: the smallest map _dgrad_actbwd takes
+    (_PE_FREE_MINP[(32, 32)] = 4096), from the smallest level input mod_up_ok takes at that size."""
+    from gans.models.ops.common import Resample
+    from gans.models.ops.native import modlayer
+    g = torch.Generator().manual_seed(91)
+    bf = torch.bfloat16
+    B, hl, wl, Ka, F, K = 2, 8, 128, 64, 256, 32
+    H, W = 2 * hl, 2 * wl
+    assert H * W == nat._PE_FREE_MINP[(K, K)]
+    spec = Resample(up=2, window=[1, 3, 3, 1], ring=True).spec
+    alpha, scale = 0.2, math.sqrt(2.0)
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(DEV)
+
+    h = rnd(B, hl, wl, Ka).to(bf).requires_grad_(True)
+    pe = rnd(1, H, W, 2 * F).to(bf)
+    W1, S1 = rnd(K, Ka + 2 * F).requires_grad_(True), rnd(B, Ka + 2 * F, scale=0.5).requires_grad_(True)
+    W2, S2 = rnd(K, K).requires_grad_(True), rnd(B, K, scale=0.5).requires_grad_(True)
+    b1, b2 = rnd(K).requires_grad_(True), rnd(K).requires_grad_(True)
+    c1, c2 = ((torch.rand(K, generator=g) + 0.5).to(DEV) for _ in range(2))
+    gy = rnd(B, H, W, K).to(bf)
+    layers = [dict(W=W1, s=S1, O=K, I=Ka + 2 * F, demod=True, cin=Ka, fw=None, group=0, row_off=0),
+              dict(W=W2, s=S2, O=K, I=K, demod=True, cin=0, fw=None, group=1, row_off=0)]
+    groups = [dict(Otot=K, I=Ka + 2 * F, dtype=bf, Ka=Ka), dict(Otot=K, I=K, dtype=bf, Ka=K)]
+    fused = []
+    inner = modlayer._dgrad_actbwd
+
+    def spy(*a):
+        r = inner(*a)
+        fused.append(r is not None)
+        return r
+
+    monkeypatch.setattr(modlayer, "_dgrad_actbwd", spy)
+
+    def grads():
+        (hd1, wb1, wt1), (hd2, wb2, wt2) = nat.mod_prep_all(layers, groups, None)
+        link = {}
+        if conv1 == "up":
+            assert nat.mod_up_ok(h, pe, wb1, spec)
+            y1 = nat.mod_up_layer(h, pe, spec, hd1, wb1, c1, bias=b1, act=True, alpha=alpha, scale=scale, wt=wt1, defer=link)
+        else:
+            y1 = nat.mod_gemm_layer(nat.resample(h, spec), pe, hd1, wb1, c1, bias=b1, act=True, alpha=alpha, scale=scale,
+                                    wt=wt1, defer=link)
+        y2 = nat.mod_gemm_layer(y1, None, hd2, wb2, c2, bias=b2, act=True, alpha=alpha, scale=scale, wt=wt2,
+                                upstream=dict(link=link, alpha=alpha, scale=scale, cvec=c1))
+        out = torch.autograd.grad(y2, [h, W1, S1, W2, S2, b2, b1], gy)
+        assert link == {}                                       # marked by conv2, read and emptied by conv1 -- or never used
+        return out
+
+    linked = grads()
+    assert fused == [True]
+    monkeypatch.setattr(modlayer, "_DGRAD_ACTBWD", False)
+    apart = grads()
+    assert fused == [True, False]
+    for a, b, name in zip(linked[:-1], apart[:-1], ("gh", "gW1", "gs1", "gW2", "gs2", "gb2")):
+        assert a.dtype == b.dtype and torch.equal(a, b), name
+    assert_rel(linked[-1].cpu(), apart[-1].cpu(), 1e-5, "conv1's bias gradient")
 
 
 def test_w_avg_update_is_one_launch_and_matches_torch():
