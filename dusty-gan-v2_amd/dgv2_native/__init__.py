@@ -230,6 +230,20 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def ptr_array(tensors):
+    """c_void_p[] of the tensors' device addresses (None -> NULL): the pointer lists of the multi-tensor entries."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def addr_array(addrs):
+    """c_void_p[] of raw device addresses (None -> NULL), for pointers into the middle of a tensor."""
+    return (ctypes.c_void_p * len(addrs))(*[None if v is None else int(v) for v in addrs])
+
+
+def int_array(vals):
+    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+
+
 ENOTSUP = -3
 
 

@@ -1,9 +1,9 @@
-"""native.act_resample: fused bias + leaky ReLU, ring-aware FIR resampler, Fourier features / angle pyramid.
+"""native.act_resample: fused bias + leaky ReLU, ring-aware FIR resampler (and the reference's upfirdn2d entry), sum of squares.
 
-Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring); the
-parts import each other in order, every name stays reachable as native.<name>.
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
 import contextlib
+import ctypes as _ct
 import math
 import os
 
@@ -11,9 +11,6 @@ import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-
-
-_EPS_U = torch.finfo(torch.float32).eps
 
 
 def _dt(t):
@@ -389,26 +386,6 @@ def resample_add(x, resid, spec, rscale=None, rbias=None):
     return resid + resample(x, spec)
 
 
-# ---------------------------------------------------------------------------------------
-# Fourier features / angle pyramid (no gradient: angles are inputs of the training path)
-# ---------------------------------------------------------------------------------------
-def fourier_feature_into(out, c0, angle, shift, freqs2, phase):
-    """Write cat(sin, cos) of the encoding into channels [c0, c0+2F) of `out` [B,H,W,ld]."""
-    B, H, W, ld = out.shape
-    F = phase.numel()
-    N.check(out, angle, shift, freqs2, phase)
-    N.call("dgv2_fourier_feature", N.ptr(out), N.ptr(angle), N.ptr(shift), N.ptr(freqs2), N.ptr(phase),
-           B, angle.shape[0], H, W, F, ld, c0, _dt(out), N.stream())
-
-
-def downsample_angle(angle, shift, taps, B, ring=True):
-    Ba, _, H, W = angle.shape
-    N.check(angle, shift, taps)
-    out = torch.empty((B, 2, H // 2, W // 2), device=angle.device, dtype=torch.float32)
-    N.call("dgv2_downsample_angle", N.ptr(out), N.ptr(angle), N.ptr(shift), N.ptr(taps), B, Ba, H, W, int(ring),
-           N.stream())
-    return out
-
 
 def sum_squares(x, C=None):
     """Sum of squares of the first C channels of a channels-last tensor as fp32 [512] PARTIAL sums (one per
@@ -421,6 +398,20 @@ def sum_squares(x, C=None):
     return acc
 
 
-import ctypes as _ct
+# ---------------------------------------------------------------------------------------
+def upfirdn2d_raw(x4, kernel, up, down, pad):
+    """x4 [major, H, W, minor] (reference extension ABI, upfirdn2d.cpp:17-31)."""
+    major, in_h, in_w, minor = x4.shape
+    kh, kw = kernel.shape
+    out_h = (in_h * up[1] + pad[2] + pad[3] - kh + down[1]) // down[1]
+    out_w = (in_w * up[0] + pad[0] + pad[1] - kw + down[0]) // down[0]
+    N.check(x4, kernel)
+    out = torch.empty((major, out_h, out_w, minor), device=x4.device, dtype=x4.dtype)
+    N.call("dgv2_upfirdn2d", N.ptr(out), N.ptr(x4), N.ptr(kernel), major, in_h, in_w, minor, kh, kw, up[0], up[1],
+           down[0], down[1], pad[0], pad[1], pad[2], pad[3], _dt(x4), N.stream())
+    return out
 
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+
+__all__ = ["input_grads_only", "want_param_grad", "bias_act", "ResampleSpec", "resample_sq", "resample", "resample_add",
+           "sum_squares", "upfirdn2d_raw", "_dt", "_bias_act_raw", "_BiasActBackward", "_SQ_CAP", "_sq_args",
+           "_resample_raw"]

@@ -1,9 +1,9 @@
 """native.conv: ring-padded dense convolution triple {fwd, dgrad, wgrad}, weight bank, fused conv nodes of the discriminator, minibatch-stddev concat, Linear.
 
-Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring); the
-parts import each other in order, every name stays reachable as native.<name>.
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
 import contextlib
+import ctypes as _ct
 import os
 from typing import NamedTuple, Optional
 
@@ -11,9 +11,10 @@ import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from . import act_resample as _act_resample
-from .act_resample import *  # noqa: F401,F403
-from .modgemm import *  # noqa: F401,F403
+from . import act_resample
+from .act_resample import ResampleSpec, _BiasActBackward, _Resample, _dt, _resample_raw, want_param_grad
+from .fp8 import _conv_fwd_fp8, _handle, _resample_q8_raw, fp8_dequant
+from .modgemm import _values
 
 
 # ---------------------------------------------------------------------------------------
@@ -317,9 +318,6 @@ _WGRAD_SCRATCH = {}
 
 
 _TN_STREAM = os.environ.get("DGV2_NO_TN_STREAM") is None           # A/B switch for benchmarking
-
-
-_TN_SCRATCH = {}
 
 
 _LIB_WGRAD = os.environ.get("DGV2_NO_LIB_WGRAD") is None         # A/B switch for benchmarking
@@ -835,8 +833,8 @@ class _FlattenNCHW(Function):
         B, H, W, C = x.shape
         out = torch.empty((B, C * H * W), device=x.device, dtype=x.dtype)
         N.check(x)
-        N.call("dgv2_transpose_list", _ptr_array([out]), _ptr_array([x]), _int_array([H * W]), _int_array([C]),
-               _int_array([C]), 1, B, x.element_size(), N.stream())
+        N.call("dgv2_transpose_list", N.ptr_array([out]), N.ptr_array([x]), N.int_array([H * W]), N.int_array([C]),
+               N.int_array([C]), 1, B, x.element_size(), N.stream())
         ctx.shape = (B, H, W, C)
         return out
 
@@ -847,8 +845,8 @@ class _FlattenNCHW(Function):
             return g.reshape(B, C, H, W).permute(0, 2, 3, 1).contiguous()
         g = g.contiguous()
         gx = torch.empty((B, H, W, C), device=g.device, dtype=g.dtype)
-        N.call("dgv2_transpose_list", _ptr_array([gx]), _ptr_array([g]), _int_array([C]), _int_array([H * W]),
-               _int_array([H * W]), 1, B, g.element_size(), N.stream())
+        N.call("dgv2_transpose_list", N.ptr_array([gx]), N.ptr_array([g]), N.int_array([C]), N.int_array([H * W]),
+               N.int_array([H * W]), 1, B, g.element_size(), N.stream())
         return gx
 
 
@@ -947,13 +945,13 @@ def conv_weight_bank(entries, dtype, image8=None):
         off8t += m8t if ft else 0
     srcs = [p.detach() for p, _, _ in entries]
     N.check(*srcs)
-    rest = (_ptr_array(srcs), _int_array([d[0] for d in dims]), _int_array([d[1] for d in dims]),
-            _int_array([d[2] for d in dims]), _int_array([d[3] for d in dims]),
+    rest = (N.ptr_array(srcs), N.int_array([d[0] for d in dims]), N.int_array([d[1] for d in dims]),
+            N.int_array([d[2] for d in dims]), N.int_array([d[3] for d in dims]),
             (_ct.c_float * L)(*[float(s) for _, s, _ in entries]), L, N.dtype_code(flat_f), N.stream())
     if image8 is None:
-        N.call("dgv2_conv_weight_bank", _ptr_array(wfs), _ptr_array(wts), *rest)
+        N.call("dgv2_conv_weight_bank", N.ptr_array(wfs), N.ptr_array(wts), *rest)
         return list(zip(wfs, wts))
-    N.call("dgv2_conv_weight_bank_ex", _ptr_array(wfs), _ptr_array(wts), _ptr_array(w8s), _ptr_array(w8ts), *rest)
+    N.call("dgv2_conv_weight_bank_ex", N.ptr_array(wfs), N.ptr_array(wts), N.ptr_array(w8s), N.ptr_array(w8ts), *rest)
     return list(zip(wfs, wts, w8s, w8ts))
 
 
@@ -973,7 +971,7 @@ def _resample_actbwd(g, out, spec, in_hw, alpha, scale):
     (ih_idx, ih_coef, ih_cnt, Eh), (iw_idx, iw_coef, iw_cnt, Ew) = spec.tables(H, W, True, g.device)
     tabs = (N.ptr(ih_idx), N.ptr(ih_coef), N.ptr(ih_cnt), Eh, N.ptr(iw_idx), N.ptr(iw_coef), N.ptr(iw_cnt), Ew)
     bands = None
-    if _act_resample._FIR_MFMA and g.dtype == torch.bfloat16 and (Ho, Wo) == (H, W) and C % 32 == 0:
+    if act_resample._FIR_MFMA and g.dtype == torch.bfloat16 and (Ho, Wo) == (H, W) and C % 32 == 0:
         bands = spec.bands(H, W, True, g.device)
     mfma = bands is not None
     entry = "dgv2_fir_same_mfma_actbwd" if mfma else "dgv2_resample_tab_actbwd"
@@ -1026,7 +1024,6 @@ class _Conv(Function):
         if resid is not None:
             resid = resid.contiguous()
         if ep.fp8 is not None:
-            from .fp8 import _conv_fwd_fp8
             _weights(ctx, w, torch.bfloat16)   # the handle's record carries the bf16 operands of the backward
             x = x8
             out = _conv_fwd_fp8(x8, ep.fp8[0], ep.fp8[1], ep.geom, bias, act, alpha, scale, resid)
@@ -1039,7 +1036,6 @@ class _Conv(Function):
         if ep.down is None:
             y = (out,)
         elif ep.q8:
-            from .fp8 import _handle, _resample_q8_raw
             y8 = _resample_q8_raw(out, ep.down, tuple(out.shape[1:3]))
             if y8 is None:
                 raise RuntimeError("dgv2: no e4m3 resampling kernel covers this shape (check native.fp8_ok first)")
@@ -1074,7 +1070,6 @@ class _Conv(Function):
         wt, w8t, gscale = ctx.bank
         gx, gw = gx_sibling, None
         if ep.fp8 is not None:   # bf16 gradients on the direct engine (no w8t), against the dequantised payload
-            from .fp8 import fp8_dequant
             if ep.resid:
                 gy = gy.contiguous()
             if ctx.needs_input_grad[0]:
@@ -1109,4 +1104,9 @@ def conv_ring(x, w, geom):
 def conv_resid_ok(x, geom):
     return _direct_ok(geom, x.shape[3] % _kstep(x) == 0)
 
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+
+__all__ = ["ConvGeom", "x3_auto", "PreparedConv", "ConvEpilogue", "linear_low", "gemm_x3", "linear_f32", "d_tail_ok",
+           "d_tail", "mbstd_cat_ok", "mbstd_cat", "flatten_nchw", "scaled_handle", "conv8t_image_ok", "conv8_image_ok",
+           "convx3_image_ok", "convx3t_image_ok", "conv_weight_bank", "conv_ring_ep", "conv_ring", "conv_resid_ok",
+           "_conv_taps", "_conv_fwd_raw", "_conv_dgrad_direct", "_conv_dgrad_raw", "_bmm_tn_small", "_conv_wgrad_raw",
+           "_resample_actbwd", "_Conv"]

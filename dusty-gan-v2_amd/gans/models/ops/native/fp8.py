@@ -1,16 +1,21 @@
 """native.fp8: e4m3 operands for the decimating branch convs of the discriminator (csrc/fp8.hip; BASELINE configs[4]).
 
-Part of gans.models.ops.native.  An e4m3 tensor never crosses an autograd edge (autograd would cast its gradient to
+An e4m3 tensor never crosses an autograd edge (autograd would cast its gradient to
 e4m3): the producers return a zero-storage bf16 HANDLE of the tensor's shape, which carries the edge, next to the e4m3
 payload (non-differentiable); the consumers take both.  First-order passes only -- R1's double backward runs the bf16
-ops (reference: the fp16 autocast switch of gans/models/dusty_v2.py:388-394)."""
+ops (reference: the fp16 autocast switch of gans/models/dusty_v2.py:388-394).
+
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
+"""
+import ctypes as _ct
 
 import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from .act_resample import *  # noqa: F401,F403
-from .conv import *  # noqa: F401,F403
+from . import act_resample
+from .act_resample import _Resample
+
 
 FP8 = torch.float8_e4m3fn
 
@@ -30,8 +35,8 @@ def fp8_quant_weights(entries):
     descale = torch.empty(L, device=dev, dtype=torch.float32)
     amax = torch.empty(L, device=dev, dtype=torch.int32)
     N.check(*srcs)
-    N.call("dgv2_fp8_quant_weights", _ptr_array(w8s), _ptr_array(srcs), _int_array([d[0] for d in dims]),
-           _int_array([d[1] for d in dims]), _int_array([d[2] for d in dims]), (_ct.c_float * L)(*[float(s) for _, s in entries]),
+    N.call("dgv2_fp8_quant_weights", N.ptr_array(w8s), N.ptr_array(srcs), N.int_array([d[0] for d in dims]),
+           N.int_array([d[1] for d in dims]), N.int_array([d[2] for d in dims]), (_ct.c_float * L)(*[float(s) for _, s in entries]),
            L, N.ptr(descale), N.ptr(amax), N.stream())
     return [(w8s[l].view(FP8), descale[l:l + 1]) for l in range(L)]
 
@@ -55,7 +60,7 @@ def _resample_q8_raw(x, spec, in_hw):
     H, W = in_hw
     oh, ow = spec.out_size(H, W)
     out = torch.empty((B, oh, ow, C), device=x.device, dtype=torch.uint8)
-    if _FIR_MFMA and (H, W) == (oh, ow) and C % 32 == 0 and oh >= _FIR_MFMA_MIN_H:
+    if act_resample._FIR_MFMA and (H, W) == (oh, ow) and C % 32 == 0 and oh >= act_resample._FIR_MFMA_MIN_H:
         bands = spec.bands(H, W, False, x.device)
         if bands is not None and N.try_call("dgv2_fir_same_mfma_q8", N.ptr(out), N.ptr(x), N.ptr(bands), B, C, oh, ow,
                                             N.stream()):
@@ -110,6 +115,4 @@ def _conv_fwd_fp8(x8, w8, descale, g, bias=None, act=0, alpha=0.2, scale=1.0, re
     return y
 
 
-import ctypes as _ct
-
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+__all__ = ["FP8", "fp8_quant_weights", "fp8_dequant", "fp8_ok", "resample_q8", "_resample_q8_raw", "_conv_fwd_fp8"]

@@ -1,13 +1,14 @@
 """native.inversion: the differentiable pieces GAN inversion needs (reference: gans/inversion.py, demo_inversion.py):
-multi-scale masked loss, range conversion with an input gradient, angle gradient of the positional encoding.
+multi-scale masked loss, range conversion (plain, and with an input gradient).  The angle gradient of the positional
+encoding is in native.fourier.
 
-Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring).
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
 import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from .act_resample import fourier_feature_into
+
 
 _METRICS = {"l1": 0, "mse": 1}
 
@@ -87,12 +88,25 @@ def msml_loss(gen, prepared, metric="l1", relative=True):
 
 
 # ---------------------------------------------------------------------------------------
-# range conversion with an input gradient (reference: autograd through CoordBridge.convert, gans/coords.py:88-185)
+# range conversion, plain and with an input gradient (reference: CoordBridge.convert and autograd through it, gans/coords.py:88-185)
 # ---------------------------------------------------------------------------------------
+def coords_convert(x, mode, min_depth, max_depth, angle=None, mask=None, raydrop_const=-1.0, out=None):
+    B, _, H, W = x.shape
+    x = x.contiguous().float()
+    N.check(x, angle, mask, out)
+    shape = (B, 3 if mode >= 2 else 1, H, W)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"coords_convert: out must be a contiguous fp32 {shape} tensor")
+    N.call("dgv2_coords_convert", N.ptr(out), N.ptr(x), N.ptr(mask), N.ptr(angle), B, H, W, float(min_depth),
+           float(max_depth), float(raydrop_const), mode, N.stream())
+    return out
+
+
 class _CoordsConvert(Function):
     @staticmethod
     def forward(ctx, x, mode, min_depth, max_depth, angle, mask, raydrop_const):
-        from .stem_tail_ada import coords_convert
         x = x.detach().contiguous().float()
         ctx.cfg = (x, mode, min_depth, max_depth, angle, mask)
         return coords_convert(x, mode, min_depth, max_depth, angle, mask, raydrop_const)
@@ -114,40 +128,4 @@ def coords_convert_diff(x, mode, min_depth, max_depth, angle=None, mask=None, ra
     return _CoordsConvert.apply(x, mode, min_depth, max_depth, angle, mask, raydrop_const)
 
 
-# ---------------------------------------------------------------------------------------
-# angle gradient of the positional encoding (reference: autograd through ops/fourier.py:77-82)
-# ---------------------------------------------------------------------------------------
-def fourier_feature_bwd(g, c0, angle, shift, freqs2, phase):
-    """g_angle (angle's shape, fp32) from the gradient `g` [B,H,W,ld] of an activation whose channels [c0, c0+2F) hold
-    the encoding of `angle` [B or 1,2,H,W] (+ shift [B] on the azimuth)."""
-    B, H, W, ld = g.shape
-    Ba = angle.shape[0]
-    out = torch.empty((B, 2, H, W), device=g.device, dtype=torch.float32)
-    N.check(g, angle, shift, freqs2, phase)
-    N.call("dgv2_fourier_feature_bwd", N.ptr(out), N.ptr(g), N.ptr(angle), N.ptr(shift), N.ptr(freqs2), N.ptr(phase),
-           B, Ba, H, W, phase.numel(), ld, c0, N.dtype_code(g), N.stream())
-    return out if Ba == B else out.sum(dim=0, keepdim=True)
-
-
-class _FourierFeature(Function):
-    @staticmethod
-    def forward(ctx, angle, shift, freqs2, phase, dtype, B):
-        _, _, H, W = angle.shape
-        angle = angle.detach().float().contiguous()
-        out = torch.empty((B, H, W, 2 * phase.numel()), device=angle.device, dtype=dtype)
-        fourier_feature_into(out, 0, angle, shift, freqs2, phase)
-        ctx.cfg = (angle, shift, freqs2, phase)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        angle, shift, freqs2, phase = ctx.cfg
-        return fourier_feature_bwd(g.contiguous(), 0, angle, shift, freqs2, phase), None, None, None, None, None
-
-
-def fourier_feature(angle, shift, freqs2, phase, dtype=torch.float32, B=None):
-    """[B,H,W,2F] channels-last encoding of `angle`, differentiable w.r.t. the angles."""
-    return _FourierFeature.apply(angle, shift, freqs2, phase, dtype, angle.shape[0] if B is None else B)
-
-
-__all__ = ["MsmlTarget", "msml_prepare", "msml_loss", "coords_convert_diff", "fourier_feature_bwd", "fourier_feature"]
+__all__ = ["MsmlTarget", "msml_prepare", "msml_loss", "coords_convert", "coords_convert_diff"]

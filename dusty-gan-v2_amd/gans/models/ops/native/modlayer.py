@@ -1,8 +1,8 @@
 """native.modlayer: one modulated-conv layer as a single autograd node, batched weight preparation of a whole generator pass.
 
-Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring); the
-parts import each other in order, every name stays reachable as native.<name>.
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
+import ctypes as _ct
 import math
 import os
 
@@ -10,10 +10,10 @@ import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from .act_resample import *  # noqa: F401,F403
-from .modgemm import *  # noqa: F401,F403
-from .conv import *  # noqa: F401,F403
-from .stem_tail_ada import *  # noqa: F401,F403
+from . import act_resample, conv, modgemm
+from .act_resample import _BiasActBackward, _bias_act_raw, _dt, _sq_args, _sq_partials
+from .conv import _bmm_tn_small
+from .modgemm import _bmm_nn_raw, bmm_nn_cat_sq_call, bmm_tn_call, bmm_tn_cat_call
 
 
 # ---------------------------------------------------------------------------------------
@@ -22,6 +22,9 @@ from .stem_tail_ada import *  # noqa: F401,F403
 # act-grad, data gradient, weight gradient, preparation backward (dgv2_mod_prep_bwd).
 # reference: ModConv2d.forward + FusedLeakyReLU, gans/models/ops/style.py:68-126, dusty_v2.py:161-170
 # ---------------------------------------------------------------------------------------
+_TN_SCRATCH = {}
+
+
 def _bmm_tn_stream(g3, xa, B, H, W_, I, O, shared=False, out=None):
     """gw fp32 [B,O,I] = per-sample sum over pixels of gy [B,H*W,O] x xa [B,H,W,I] (dgv2_bmm_tn_stream); shared: xa is
     one image [1,H,W,I] contracted against every sample (the positional encoding).  out: a [B,O,ld] fp32 tensor
@@ -45,8 +48,8 @@ def _pe_cat_fwd(out, xa, xs, wb, cvec, bias32, act, cfg, sq):
     B, H, W_, Otot = out.shape
     Ka = 0 if xa is None else xa.shape[3]
     Ks = xs.shape[3]
-    tail = (N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
-    if _PE_FWD and out.dtype == torch.bfloat16 and (Ka, Ks, Otot) in ((64, 512, 32), (128, 512, 64), (256, 512, 128)):
+    tail = (N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
+    if modgemm._PE_FWD and out.dtype == torch.bfloat16 and (Ka, Ks, Otot) in ((64, 512, 32), (128, 512, 64), (256, 512, 128)):
         # top pyramid levels: pixel-tile blocks walking the samples, PE fragments in registers
         N.call("dgv2_modconv_pe_fwd_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, H * W_, Ka, Ks, Otot, N.ptr(cvec),
                N.ptr(bias32), act, cfg["alpha"], cfg["scale"], _dt(xs), *tail)
@@ -93,7 +96,7 @@ class _ModLayer(Function):
         act = 3 if cfg["act"] else 0
         bias32 = None if bias is None else bias.detach().float().contiguous()
         odt = cfg["out_dtype"]
-        sq = _sq_args(dev) if (cfg["want_sq"] and _FUSED_SQ) else None
+        sq = _sq_args(dev) if (cfg["want_sq"] and act_resample._FUSED_SQ) else None
         if xs is not None:
             xs = xs.contiguous()
             xa = None if xa is None else xa.contiguous()
@@ -208,14 +211,14 @@ class _ModPrepAll(Function):
         rot = shift is not None
         flags = [(1 if m["demod"] else 0) | (2 if (rot and m["fw"] is not None) else 0)
                  | (4 if meta["groups"][m["group"]]["dtype"] == torch.bfloat16 else 0) for m in lay]
-        ints = dict(O=_int_array([m["O"] for m in lay]), I=_int_array([m["I"] for m in lay]),
-                    Otot=_int_array([meta["groups"][m["group"]]["Otot"] for m in lay]),
-                    row_off=_int_array([m["row_off"] for m in lay]), cin=_int_array([m["cin"] for m in lay]),
-                    flags=_int_array(flags))
+        ints = dict(O=N.int_array([m["O"] for m in lay]), I=N.int_array([m["I"] for m in lay]),
+                    Otot=N.int_array([meta["groups"][m["group"]]["Otot"] for m in lay]),
+                    row_off=N.int_array([m["row_off"] for m in lay]), cin=N.int_array([m["cin"] for m in lay]),
+                    flags=N.int_array(flags))
         N.check(*Ws, *Ss, shift, *[f for f in fws if f is not None])
-        N.call("dgv2_mod_prep_all_fwd", _ptr_array([wbs[m["group"]] for m in lay]), _ptr_array(dsaves), N.ptr(stats),
-               N.ptr(rot_tab), _ptr_array(Ws), _ptr_array(Ss), _ptr_array(fws), ints["O"], ints["I"], ints["Otot"], ints["row_off"],
-               ints["cin"], ints["flags"], N.ptr(shift) if rot else None, B, L, N.stream())
+        N.call("dgv2_mod_prep_all_fwd", N.ptr_array([wbs[m["group"]] for m in lay]), N.ptr_array(dsaves), N.ptr(stats),
+               N.ptr(rot_tab), N.ptr_array(Ws), N.ptr_array(Ss), N.ptr_array(fws), ints["O"], ints["I"], ints["Otot"],
+               ints["row_off"], ints["cin"], ints["flags"], N.ptr(shift) if rot else None, B, L, N.stream())
         ctx.meta, ctx.ints, ctx.B, ctx.rot = meta, ints, B, rot
         ctx.save_for_backward(shift, stats, dflat, rot_tab, *Ws, *Ss)
         handles = [torch.empty(1, device=dev, dtype=torch.float32).expand(B, g["Otot"], g["I"]) for g in meta["groups"]]
@@ -226,9 +229,9 @@ class _ModPrepAll(Function):
         for es in (2, 4):
             sel = [k for k in idx if wts[k].element_size() == es]
             if sel:
-                N.call("dgv2_transpose_list", _ptr_array([wts[k] for k in sel]), _ptr_array([wbs[k] for k in sel]),
-                       _int_array([meta["groups"][k]["Otot"] for k in sel]), _int_array([meta["groups"][k]["Ka"] for k in sel]),
-                       _int_array([meta["groups"][k]["I"] for k in sel]), len(sel), B, es, N.stream())
+                N.call("dgv2_transpose_list", N.ptr_array([wts[k] for k in sel]), N.ptr_array([wbs[k] for k in sel]),
+                       N.int_array([meta["groups"][k]["Otot"] for k in sel]), N.int_array([meta["groups"][k]["Ka"] for k in sel]),
+                       N.int_array([meta["groups"][k]["I"] for k in sel]), len(sel), B, es, N.stream())
         ctx.mark_non_differentiable(*wbs, *wts)
         return (*handles, *wbs, *wts)
 
@@ -266,9 +269,9 @@ class _ModPrepAll(Function):
             N.call("dgv2_mod_prep_all_bwd_scratch", _ct.addressof(n), ints["O"], ints["I"], B, L)
             _TN_SCRATCH[key] = n.value
         scratch = torch.empty(_TN_SCRATCH[key], device=dev, dtype=torch.float32)
-        N.call("dgv2_mod_prep_all_bwd", N.ptr(flat), flat.numel(), _ptr_array(outs), _int_array(ncorr),
-               _ptr_array([Gs[m["group"]] for m in lay]), _ptr_array(list(Ws)), _ptr_array(list(Ss)), N.ptr(stats),
-               N.ptr(rot_tab), _ptr_array(dsaves), _ptr_array([m["fw"] for m in lay]), ints["O"], ints["I"], ints["Otot"],
+        N.call("dgv2_mod_prep_all_bwd", N.ptr(flat), flat.numel(), N.ptr_array(outs), N.int_array(ncorr),
+               N.ptr_array([Gs[m["group"]] for m in lay]), N.ptr_array(list(Ws)), N.ptr_array(list(Ss)), N.ptr(stats),
+               N.ptr(rot_tab), N.ptr_array(dsaves), N.ptr_array([m["fw"] for m in lay]), ints["O"], ints["I"], ints["Otot"],
                ints["row_off"], ints["cin"], ints["flags"], N.ptr(shift) if ctx.rot else None, B, L, N.ptr(scratch),
                scratch.numel(), N.stream())
         res = []
@@ -355,7 +358,7 @@ class _ModGemmPrepared(Function):
         act = 3 if cfg["act"] else 0
         bias32 = None if bias is None else bias.detach().float().contiguous()
         odt = cfg["out_dtype"]
-        sq = _sq_args(dev) if (cfg["want_sq"] and _FUSED_SQ) else None
+        sq = _sq_args(dev) if (cfg["want_sq"] and act_resample._FUSED_SQ) else None
         N.check(xa, xs, wb, bias32, cvec)
         if xs is not None:
             xs = xs.contiguous()
@@ -494,19 +497,19 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
     layer is chosen: _ModLayer, _ModGemmPrepared and the full-resolution PE columns of _ModUpPrepared all come here."""
     P = H * W_
     Ka = 0 if xa is None else xa.shape[3]
-    if (xs is not None and xa is not None and _LIB_WGRAD and dt == torch.bfloat16 and P >= 2048 and _TN_STREAM and Ka % 8 == 0
-            and Otot % 8 == 0 and I % 4 == 0 and Ka % 4 == 0):
+    if (xs is not None and xa is not None and conv._LIB_WGRAD and dt == torch.bfloat16 and P >= 2048 and conv._TN_STREAM
+            and Ka % 8 == 0 and Otot % 8 == 0 and I % 4 == 0 and Ka % 4 == 0):
         # both column ranges of the [B, Otot, Ka + Ks] gradient written in place by their engines: no concatenation
         gwb = torch.empty((B, Otot, I), device=g3.device, dtype=torch.float32)
         if pe_wgrad(g3, xs.reshape(P, -1), out=gwb, col0=Ka) is not None:
             _bmm_tn_stream(g3, xa, B, H, W_, Ka, Otot, out=gwb)
             return gwb
-    if xs is not None and _LIB_WGRAD and dt == torch.bfloat16 and P >= 2048:
+    if xs is not None and conv._LIB_WGRAD and dt == torch.bfloat16 and P >= 2048:
         # plain batched GEMMs (K = pixels of one sample, fp32 out): hipBLASLt's split-K kernels beat the
         # generic dgv2 TN kernel on these long-K / short-M shapes; the batch-shared PE is a stride-0 operand
         gT = g3.transpose(1, 2)
         parts = []
-        if xa is not None and _TN_STREAM and Ka % 8 == 0 and Otot % 8 == 0:
+        if xa is not None and conv._TN_STREAM and Ka % 8 == 0 and Otot % 8 == 0:
             parts.append(_bmm_tn_stream(g3, xa, B, H, W_, Ka, Otot))   # own streaming engine, per sample
         elif xa is not None:
             parts.append(torch.bmm(gT, xa.reshape(B, P, Ka), out_dtype=torch.float32))
@@ -518,7 +521,7 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
         gwb = torch.empty((B, Otot, I), device=g3.device, dtype=torch.float32)
         bmm_tn_cat_call(N.ptr(gwb), N.ptr(g3), N.ptr(xa), N.ptr(xs), B, P, Ka, xs.shape[3], Otot, _dt(xs), N.stream())
         return gwb
-    if _TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
+    if conv._TN_STREAM and dt == torch.bfloat16 and P >= 2048 and I % 8 == 0 and Otot % 8 == 0:
         # dense layers of the top levels: the streaming split-K engine of the conv weight gradient, per sample
         return _bmm_tn_stream(g3, xa, B, H, W_, I, Otot)
     if Otot <= 4 and g3.dtype == xa.dtype:
@@ -549,7 +552,7 @@ def _dgrad_actbwd(g3, wt, xa, up):
     K = wt.shape[1]
     if (not _DGRAD_ACTBWD or g3.dtype != torch.bfloat16 or xa.dtype != torch.bfloat16 or wt.dtype != torch.bfloat16
             or K != O or K not in (32, 64) or tuple(wt.shape) != (B, K, O)
-            or P < _PE_FREE_MINP.get((O, K), 1 << 30) or up.get("link") is None):
+            or P < modgemm._PE_FREE_MINP.get((O, K), 1 << 30) or up.get("link") is None):
         return None
     key = (B, P, K)
     if key not in _DGRAD_ACT_ROWS:
@@ -637,4 +640,5 @@ def _head_bwd_fused(gy, cvec, wt, resid, xa, up):
     return y, gwb, gbh
 
 
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+__all__ = ["mod_layer", "mod_prep_all", "mod_gemm_layer", "pe_wgrad", "_bmm_tn_stream", "_mod_act_bwd", "_mod_wgrad",
+           "_dgrad_actbwd", "_head_dgrad_actbwd"]

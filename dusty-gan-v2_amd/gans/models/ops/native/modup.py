@@ -1,8 +1,8 @@
-"""native.misc: KITTI projection, fused non-saturating objective, conv1 with the up-sampling commuted past the contraction.
+"""native.modup: conv1 of a generator level with the block's up-sampling commuted past the contraction (csrc/modconv_up.hip).
 
-Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring); the
-parts import each other in order, every name stays reachable as native.<name>.
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
+import ctypes as _ct
 import math
 import os
 
@@ -10,137 +10,10 @@ import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from .act_resample import *  # noqa: F401,F403
-from .modgemm import *  # noqa: F401,F403
-from .conv import *  # noqa: F401,F403
-from .stem_tail_ada import *  # noqa: F401,F403
-from .modlayer import *  # noqa: F401,F403
-
-
-# ---------------------------------------------------------------------------------------
-# KITTI scan -> range image (dgv2_kitti_project; reference: gans/datasets/kitti.py:264-279,317-370)
-# ---------------------------------------------------------------------------------------
-def kitti_rows(points, H):
-    """points fp32 [n,4] CUDA (file order) -> int32 [n] ring index per point (scan unfolding), see dgv2_kitti_rows."""
-    points = points.contiguous()
-    N.check(points)
-    n = points.shape[0]
-    rows = torch.empty(n, device=points.device, dtype=torch.int32)
-    counts = torch.empty((n + 4095) // 4096 + 1, device=points.device, dtype=torch.int32)
-    N.call("dgv2_kitti_rows", N.ptr(rows), N.ptr(counts), N.ptr(points), n, int(H), N.stream())
-    return rows
-
-
-def kitti_project(points, rows, H, W, Wout, min_depth, max_depth, apply_mask=True):
-    """points fp32 [n,4] CUDA; rows int32 [n] (scan-unfolding ring index per point) or None (pitch-angle rows).
-    -> fp32 [6, H, Wout]: x, y, z, reflectance, depth, mask of the nearest point of pixel (h, w * W / Wout)."""
-    n = points.shape[0]
-    out = torch.empty((6, H, Wout), device=points.device, dtype=torch.float32)
-    key = torch.empty(H * W, device=points.device, dtype=torch.int64)
-    N.check(points, rows)
-    N.call("dgv2_kitti_project", N.ptr(out), N.ptr(key), N.ptr(points), N.ptr(rows), n, H, W, Wout, float(min_depth),
-           float(max_depth), int(apply_mask), N.stream())
-    return out
-
-
-# ---------------------------------------------------------------------------------------
-# non-saturating GAN objective + logged statistics in one launch (dgv2_nsgan_loss)
-# ---------------------------------------------------------------------------------------
-class _NsganLoss(Function):
-    """loss = mean softplus(-y[:n_real]) + mean softplus(y[n_real:]); also returns (no gradient) the 4 statistics
-    [loss, mean y_real, mean y_fake, sum sign(y_real)].  First order only (the R1 penalty does not go through it)."""
-
-    @staticmethod
-    def forward(ctx, y, n_real):
-        yf = y.detach().float().contiguous().reshape(-1)
-        n = yf.numel()
-        stats = torch.empty(4, device=y.device, dtype=torch.float32)
-        gy = torch.empty(n, device=y.device, dtype=torch.float32)
-        N.check(yf)
-        N.call("dgv2_nsgan_loss", N.ptr(stats), N.ptr(gy), N.ptr(yf), int(n_real), n - int(n_real), 1.0, None, None, N.stream())
-        ctx.save_for_backward(gy)
-        ctx.shape, ctx.dtype = y.shape, y.dtype
-        ctx.mark_non_differentiable(stats)
-        return stats[0].clone(), stats
-
-    @staticmethod
-    def backward(ctx, g, _):
-        (gy,) = ctx.saved_tensors
-        return (gy * g).reshape(ctx.shape).to(ctx.dtype), None
-
-
-def nsgan_loss(y, n_real):
-    """(loss, stats[4]) for logits y [n,1] with the first n_real rows judged as real (see _NsganLoss)."""
-    return _NsganLoss.apply(y, n_real)
-
-
-def nsgan_step(y, n_real, weight=1.0, cum=None):
-    """The objective of a step body WITHOUT a scalar-loss graph: (stats[4], gy) with gy = weight * d loss / d y shaped like
-    y -- the cotangent the body hands to y.backward(gy).  One launch; `(weight * loss).backward()` costs a clone, a scalar
-    multiply, the ones_like seed, the multiply's backward and the broadcast product with the saved gradient on top.
-    cum = (sign_cum, n_pred_cum): AdaptiveAugment's fp32 [1] buffers, updated in the same launch (its `cumulate`)."""
-    yf = y.detach().float().contiguous().reshape(-1)
-    n = yf.numel()
-    stats = torch.empty(4, device=y.device, dtype=torch.float32)
-    gy = torch.empty(n, device=y.device, dtype=torch.float32)
-    N.check(yf)
-    sc, nc = (None, None) if cum is None else cum
-    if cum is not None and not all(t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 for t in cum):
-        raise ValueError("nsgan_step: cum = (sign_cum, n_pred_cum), fp32 [1] device tensors")
-    N.call("dgv2_nsgan_loss", N.ptr(stats), N.ptr(gy), N.ptr(yf), int(n_real), n - int(n_real), float(weight), N.ptr(sc),
-           N.ptr(nc), N.stream())
-    return stats, gy.reshape(y.shape).to(y.dtype)
-
-
-# ---------------------------------------------------------------------------------------
-# every random number of a step body from one launch (dgv2_rng_fill, csrc/rng.hip)
-# ---------------------------------------------------------------------------------------
-_RNG_STATE = {}
-RNG_UNIFORM, RNG_NORMAL, RNG_CLAMPED, RNG_BERNOULLI = 0, 1, 2, 3
-
-
-def rng_state(device=None, seed=None):
-    """The Philox stream of `device` (int64[4] device tensor: seed, offset, ticket, unused), created on first use from
-    torch's seed of that moment (torch.initial_seed(): init_random_seed / manual_seed decide it, per rank).  `seed`
-    re-seeds the stream and rewinds it.  Must exist before a hipGraph capture that draws from it."""
-    idx = torch.cuda.current_device() if device is None else torch.device(device).index
-    idx = torch.cuda.current_device() if idx is None else idx
-    st = _RNG_STATE.get(idx)
-    if st is None or seed is not None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("dgv2: the RNG stream must exist before a hipGraph capture (native.rng_state())")
-        sd = torch.initial_seed() if seed is None else int(seed)
-        vals = torch.tensor([sd & 0x7FFFFFFFFFFFFFFF, 0, 0, 0], dtype=torch.int64)
-        if st is None:
-            st = _RNG_STATE[idx] = vals.to(torch.device("cuda", idx))
-        else:
-            st.copy_(vals)
-    return st
-
-
-def rng_fill(specs, device):
-    """specs: list of (shape, kind, a, b) -> list of fp32 tensors (views of one allocation), ONE launch.
-    kind RNG_UNIFORM: uniform in [a, b); RNG_NORMAL: mean a, std b; RNG_CLAMPED: u in [0, 1) clamped to [a, b];
-    RNG_BERNOULLI: 1.0 with probability a, else 0.0."""
-    if not 1 <= len(specs) <= 16:
-        raise ValueError("rng_fill takes 1..16 segments")
-    counts = [int(math.prod(sh)) for sh, _, _, _ in specs]
-    offs, tot = [], 0
-    for c in counts:
-        offs.append(tot)
-        tot += (c + 3) // 4 * 4            # 16-byte aligned segments: whole float4 stores
-    st = rng_state(device)
-    buf = torch.empty(tot, device=device, dtype=torch.float32)
-    outs = [buf[o:o + c].view(sh) for o, c, (sh, _, _, _) in zip(offs, counts, specs)]
-    import ctypes as _c
-    n = len(specs)
-    ptrs = (_c.c_void_p * n)(*[t.data_ptr() for t in outs])
-    cnt = (_c.c_int64 * n)(*counts)
-    kinds = (_c.c_int * n)(*[int(k) for _, k, _, _ in specs])
-    a = (_c.c_float * n)(*[float(v) for _, _, v, _ in specs])
-    b = (_c.c_float * n)(*[float(v) for _, _, _, v in specs])
-    N.call("dgv2_rng_fill", ptrs, cnt, kinds, a, b, n, N.ptr(st), N.stream())
-    return outs
+from . import act_resample, conv
+from .act_resample import _dt, _resample_raw, _sq_args, _sq_partials
+from .modgemm import _bmm_nn_raw, bmm_tn_call
+from .modlayer import _bmm_tn_stream, _mod_act_bwd, _mod_wgrad, pe_wgrad
 
 
 # ---------------------------------------------------------------------------------------
@@ -229,7 +102,7 @@ def up2_lag_sumsq(x, spec):
     sq = _sq_args(x.device)
     N.check(x)
     if not N.try_call("dgv2_up2_lag_sumsq", N.ptr(x), N.ptr(gram[0]), N.ptr(gram[1]), N.ptr(gram[2]), N.ptr(gram[3]), B,
-                      H, W, C, _dt(x), N.ptr(sq[0]), _SQ_CAP, _ct.addressof(sq[1]), N.stream()):
+                      H, W, C, _dt(x), N.ptr(sq[0]), act_resample._SQ_CAP, _ct.addressof(sq[1]), N.stream()):
         return None
     return sq[0][:sq[1].value]
 
@@ -283,7 +156,7 @@ def resample_sq_only(x, spec):
     C = x.shape[3]
     N.check(x)
     N.call("dgv2_resample_tab_sq", None, N.ptr(x), N.ptr(ih_idx), N.ptr(ih_coef), N.ptr(ih_cnt), Eh, N.ptr(iw_idx),
-           N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, C, C, H, W, Ho, Wo, _dt(x), N.ptr(sq[0]), _SQ_CAP,
+           N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, C, C, H, W, Ho, Wo, _dt(x), N.ptr(sq[0]), act_resample._SQ_CAP,
            _ct.addressof(sq[1]), N.stream())
     return sq[0][:sq[1].value]
 
@@ -321,7 +194,7 @@ def mod_up_prepare(h, xs, wb, spec, act=True, alpha=0.2, scale=math.sqrt(2.0), w
     N.check(h, wb)
     if not N.try_call("dgv2_modconv_up_t_lag", N.ptr(t), N.ptr(wimg), N.ptr(h), N.ptr(wb), gain,
                       *(N.ptr(g) for g in (gram if gram is not None else (None,) * 4)), B, hl, wl, Ka, Ks, Otot, I, Ka,
-                      _dt(h), N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0,
+                      _dt(h), N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0,
                       _ct.addressof(sq[1]) if sq else None, N.stream()):
         return None
     return t, wimg, (sq[0][:sq[1].value] if sq else None)
@@ -353,13 +226,13 @@ class _ModUpPrepared(Function):
             N.call("dgv2_modconv_up_t", N.ptr(t), N.ptr(wimg), N.ptr(h), N.ptr(wb), N.ptr(cvec), gain, B, hl, wl, Ka, Ks,
                    Otot, I, Ka, _dt(h), N.stream())
         ih, ch, iw, cw = _up_tables(spec, hl, wl, dev)
-        sq = _sq_args(dev) if (cfg["want_sq"] and _FUSED_SQ) else None
+        sq = _sq_args(dev) if (cfg["want_sq"] and act_resample._FUSED_SQ) else None
         out = torch.empty((B, H, W_, Otot), device=dev, dtype=dt)
         xsf = pe_frag16(xs)
         N.check(t, xsf, wimg, bias32, cvec)
         N.call("dgv2_modconv_up_fwd", N.ptr(out), N.ptr(t), N.ptr(xsf), N.ptr(wimg), B, H, W_, hl, wl, Ks, Otot,
                N.ptr(ih), N.ptr(ch), N.ptr(iw), N.ptr(cw), N.ptr(bias32), N.ptr(in_scale), act, cfg["alpha"],
-               cfg["scale"], _dt(h), N.ptr(sq[0]) if sq else None, _SQ_CAP if sq else 0,
+               cfg["scale"], _dt(h), N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0,
                _ct.addressof(sq[1]) if sq else None, N.stream())
         ctx.cfg = dict(cfg, has_bias=bias is not None)
         ctx.save_for_backward(h, xs, wb, out if cfg["act"] else None, cvec, wt)
@@ -395,7 +268,7 @@ class _ModUpPrepared(Function):
                     wt = wb[:, :, :Ka].transpose(1, 2).contiguous()
                 gh = _bmm_nn_raw(gt3, wt, h.dtype).reshape(h.shape)
             Ks = xs.shape[3]
-            stream_a = _TN_STREAM and Ka % 8 == 0 and Otot % 8 == 0 and hl * wl >= 2048
+            stream_a = conv._TN_STREAM and Ka % 8 == 0 and Otot % 8 == 0 and hl * wl >= 2048
             if need_w and stream_a and (Ka + Ks) % 4 == 0 and Ka % 4 == 0:
                 # both column ranges of the [B, Otot, Ka + Ks] gradient written in place by their engines (the PE columns
                 # at full resolution, the activation columns at the low one): no concatenation pass
@@ -428,4 +301,5 @@ def mod_up_layer(h, xs, spec, handle, wb, cvec, bias=None, act=True, alpha=0.2, 
     return _ModUpPrepared.apply(cfg, h, xs, bias, handle, wb, cvec, wt, t, wimg)
 
 
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+__all__ = ["up2_lag_sumsq", "pe_frag16", "mod_up_ok", "resample_sq_only", "mod_up_image_shapes", "mod_up_images",
+           "mod_up_prepare", "mod_up_layer", "_up_tables"]

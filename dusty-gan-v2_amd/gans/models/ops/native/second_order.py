@@ -14,8 +14,8 @@ import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from .act_resample import *  # noqa: F401,F403
-from .modgemm import *  # noqa: F401,F403
+from .act_resample import _dt
+from .modgemm import _bmm_nn_raw, _bmm_tn_raw
 
 
 def _cat_nn(xa, xs, wc, out_dtype):
@@ -105,4 +105,4 @@ def cat_gemm(xa, xs, w, out_dtype=None):
     return y.reshape(w.shape[0], *shp[1:-1], w.shape[1])
 
 
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+__all__ = ["cat_gemm"]

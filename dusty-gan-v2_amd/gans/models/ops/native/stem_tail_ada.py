@@ -1,18 +1,15 @@
-"""native.stem_tail_ada: discriminator stem, generator output stage, ADA separable operator, upfirdn2d.
+"""native.stem_tail_ada: discriminator stem, generator output stage, Gumbel uniforms, ADA operator and image-space stages.
 
-Part of gans.models.ops.native (autograd-aware wrappers around the libdgv2 C ABI, see the package docstring); the
-parts import each other in order, every name stays reachable as native.<name>.
+Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
+import ctypes as _ct
 import math
-import os
 
 import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from .act_resample import *  # noqa: F401,F403
-from .modgemm import *  # noqa: F401,F403
-from .conv import *  # noqa: F401,F403
+from .act_resample import _dt, _resample_raw
 
 
 # ---------------------------------------------------------------------------------------
@@ -128,6 +125,9 @@ class _GenTail(Function):
 def gen_tail(skip, shift, u, out_scale=0.25, raydrop_const=-1.0, temperature=1.0):
     """skip fp32 [B,H,W,2] -> (image, image_orig, raydrop_logit, raydrop_mask), each [B,1,H,W]."""
     return _GenTail.apply(skip, shift, u, float(out_scale), float(raydrop_const), float(temperature))
+
+
+_EPS_U = torch.finfo(torch.float32).eps
 
 
 def gumbel_uniform(shape, device):
@@ -275,31 +275,5 @@ def ada_fold(Ay, kx, off, sgn, c, g, fbank, W):
     return Ay2, kx2, off2, c2
 
 
-# ---------------------------------------------------------------------------------------
-def upfirdn2d_raw(x4, kernel, up, down, pad):
-    """x4 [major, H, W, minor] (reference extension ABI, upfirdn2d.cpp:17-31)."""
-    major, in_h, in_w, minor = x4.shape
-    kh, kw = kernel.shape
-    out_h = (in_h * up[1] + pad[2] + pad[3] - kh + down[1]) // down[1]
-    out_w = (in_w * up[0] + pad[0] + pad[1] - kw + down[0]) // down[0]
-    N.check(x4, kernel)
-    out = torch.empty((major, out_h, out_w, minor), device=x4.device, dtype=x4.dtype)
-    N.call("dgv2_upfirdn2d", N.ptr(out), N.ptr(x4), N.ptr(kernel), major, in_h, in_w, minor, kh, kw, up[0], up[1],
-           down[0], down[1], pad[0], pad[1], pad[2], pad[3], _dt(x4), N.stream())
-    return out
-
-
-def coords_convert(x, mode, min_depth, max_depth, angle=None, mask=None, raydrop_const=-1.0, out=None):
-    B, _, H, W = x.shape
-    x = x.contiguous().float()
-    N.check(x, angle, mask, out)
-    shape = (B, 3 if mode >= 2 else 1, H, W)
-    if out is None:
-        out = torch.empty(shape, device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"coords_convert: out must be a contiguous fp32 {shape} tensor")
-    N.call("dgv2_coords_convert", N.ptr(out), N.ptr(x), N.ptr(mask), N.ptr(angle), B, H, W, float(min_depth),
-           float(max_depth), float(raydrop_const), mode, N.stream())
-    return out
-
-__all__ = [n_ for n_ in dir() if not n_.startswith("__")]
+__all__ = ["stem", "gen_tail", "gumbel_uniform", "ada_apply", "ada_sample", "ada_build", "ada_apply_img", "ada_sample_img",
+           "ada_fold"]

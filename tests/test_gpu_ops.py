@@ -891,7 +891,7 @@ def test_grouped_linear_style_affines_and_mapping_network(nat, B, shared, monkey
     as ONE launch (styles expanded from one vector -- the training case -- or a [B, S, K] tensor with per-layer style
     indices) and the mapping network (PixelNorm + two EqualLR Linear + LeakyReLU, dusty_v2.py:13-29), values and every
     gradient against float64 torch ops (reference: style.py:30,75, common.py:158-184,213-223)."""
-    monkeypatch.setattr(nat.modgemm, "_GLIN_GRAD", True)     # (default: gradient-recording passes keep the library calls)
+    monkeypatch.setattr(nat.glin, "_GLIN_GRAD", True)        # (default: gradient-recording passes keep the library calls)
     g = torch.Generator().manual_seed(3 + B)
     K, S = 512, 10
     Is = [512, 512, 512, 1024, 256, 256, 256, 768, 128, 128, 128, 640, 64, 64, 64, 576, 32, 32, 32]
@@ -1878,12 +1878,13 @@ def _dense_rows(idx, coef, cnt, L):
 
 @pytest.mark.parametrize("B,H,W,C", [(2, 64, 512, 32), (3, 16, 64, 64), (2, 8, 32, 128), (1, 24, 96, 32), (2, 128, 64, 32)])
 @pytest.mark.parametrize("adjoint", [False, True])
-def test_fir_same_size_on_mfma(nat, B, H, W, C, adjoint):
+def test_fir_same_size_on_mfma(nat, B, H, W, C, adjoint, monkeypatch):
     """Blur (and its adjoint) through dgv2_fir_same_mfma: against the dense resampling matrices in float64 and against
     the table-driven kernel it replaces (same rounding points; only the fp32 summation order differs)."""
     import dgv2_native as N
     from gans.models.ops.native import act_resample as ar
-    ar._FIR_MFMA_MIN_H = 8   # the router sends maps under 32 rows to the table-driven kernel; here the MFMA kernel runs them
+    # the router sends maps under 32 rows to the table-driven kernel; here the MFMA kernel runs them
+    monkeypatch.setattr(ar, "_FIR_MFMA_MIN_H", 8)
     spec = nat.ResampleSpec([1, 3, 3, 1])
     assert spec.mfma_ok(H, W, adjoint, DEV) and spec.bands(H, W, adjoint, DEV) is not None
     g = torch.Generator().manual_seed(H * W + C + int(adjoint))
