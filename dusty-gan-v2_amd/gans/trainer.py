@@ -16,6 +16,7 @@ import copy
 import gc
 import os
 from collections import defaultdict
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -52,6 +53,31 @@ def ema_inplace(ema_model, new_model, decay):
 
 # per-site keys of AdaptiveAugment.forward's `draws`: parity forms (G, C / g, sigma, cut) and raw forms (u, n / u2, n2), eps
 _ADA_DRAW_KEYS = ("G", "C", "u", "n", "g", "sigma", "cut", "u2", "n2", "eps")
+
+
+class StepPlan(NamedTuple):
+    """What one iteration will do, decided at the top of Trainer.step (Trainer._plan) and read by every sub-step; the
+    two properties say how G's and D's gradients are exchanged and applied (Trainer._reduce_start / _reduce_finish)."""
+    nacc: int            # chunks per iteration (gradient accumulation)
+    dist: bool           # there is someone to exchange with (parallel.is_dist())
+    split_d: bool        # D's backward runs in two pieces (d_fb_head / d_fb_tail), the head's gradients leave in between
+    fused: bool          # one process, one chunk: forward / backward and Adam of a sub-step are ONE body (g_step, ...)
+    fuse_d: bool         # ... for D and R1 too: not when D's backward runs in two pieces
+    fold: bool           # RCCL + graphs: the small reductions ride inside the optimizer graphs (never with `fused`)
+    late_reals: bool     # the real batch is fetched behind G's backward, under G's reduction
+    part_rest: Optional[str]   # the segment of D's gradient that its optimizer step waits for: "rest" behind a split D
+    captured_tail: bool  # the tail exchange replays as a graph
+    r1_due: bool
+    pl_due: bool
+    ada_due: bool
+
+    @property
+    def g_exchange(self):
+        return "none" if self.fused else "fold" if self.fold else "async"
+
+    @property
+    def d_exchange(self):
+        return "none" if self.fuse_d else "fold" if self.fold else "async"
 
 
 class Trainer:
@@ -398,25 +424,13 @@ class Trainer:
     # One process, one chunk: nothing happens between a body's backward and its optimizer step (no exchange, no second
     # chunk), so both are ONE body -- one graph launch instead of two, and Adam reads the gradients where the backward
     # left them (FlatGradSync.collect(pack=False): no pack copy, 40 us of multi-tensor launches for G's 140 tensors).
-    def g_fb_opt(self, j, scalars):
-        self.g_fb(j, scalars, pack=False)
-        self._opt_step(self.optim_G)
+    def _fb_opt(self, fb, opt, *args):   # g_step / d_step / r1_step: the body `fb(*args)` (scalars last), then Adam
+        fb(*args, pack=False)
+        self._opt_step(opt)
 
-    def g_fb_rel_opt(self, x_real, j, scalars):
-        self.g_fb(j, scalars, x_real, pack=False)
-        self._opt_step(self.optim_G)
-
-    def d_fb_opt(self, x_real, j, scalars):
-        self.d_fb(x_real, j, scalars, pack=False)
-        self._opt_step(self.optim_D)
-
-    def r1_fb_opt(self, x_real, j, scalars):
-        self.r1_fb(x_real, j, scalars, pack=False)
-        self._opt_step(self.optim_D)
-
-    def g_fb_rel(self, x_real, j, scalars):
+    def g_fb_rel(self, x_real, j, scalars, pack=True):
         """G step of a relativistic objective: also D(A(real)) (argument order of the other bodies that take reals)."""
-        self.g_fb(j, scalars, x_real)
+        self.g_fb(j, scalars, x_real, pack)
 
     def d_fb(self, x_real, j, scalars, cut=False, pack=True):
         set_requires_grad(self.D, True)
@@ -552,27 +566,34 @@ class Trainer:
         return 0.5 ** (self.batch_size / max(ema_imgs, 1e-8))
 
     # ------------------------------------------------------------------ hipGraph plumbing
-    def _graphs_usable(self):
-        return self.use_graphs
-
     def _run(self, name, fn, *args):
         """Run `fn(*args, scalars)` eagerly, or capture it once as a hipGraph and replay it.
         Returns the dict of scalar tensors the body produced (static buffers under replay)."""
         only = os.environ.get("DGV2_GRAPHS")  # debugging aid: comma list of bodies allowed to be graphs
-        if not self._graphs_usable() or (only is not None and name not in only.split(",")):
+        graph = None
+        if self.use_graphs and (only is None or name in only.split(",")):
+            if self._warm() and not name.endswith("_opt"):
+                name = name + "/warmup"   # the fade-in regime has its own captures (extra blur / dropout work)
+            if self._injected is not None and not name.endswith("_opt"):
+                name = name + "/inj"      # bodies that read injected draws are different graphs than the sampling ones
+            graph = self._captured(name, fn, args)
+        if graph is None:
             scalars = {}
             fn(*args, scalars)
             return scalars
-        if self._warm() and not name.endswith("_opt"):
-            name = name + "/warmup"   # the fade-in regime has its own captures (extra blur / dropout work)
-        if self._injected is not None and not name.endswith("_opt"):
-            name = name + "/inj"      # bodies that read injected draws are different graphs than the sampling ones
+        g, scalars = graph
+        g.replay()
+        if os.environ.get("DGV2_GRAPH_SYNC"):  # debugging aid: serialise host and device after each replay
+            torch.cuda.synchronize()
+        return scalars
+
+    def _captured(self, name, fn, args):
+        """(graph, scalars) of the body `name`, captured on its third call; None while it warms up (allocator /
+        autotune) and, for good, after a capture that failed: the caller runs the body eagerly."""
         if name not in self._graphs:
-            if self._graph_warm.get(name, 0) < 2:  # allocator / autotune warm-up before capture
+            if self._graph_warm.get(name, 0) < 2:
                 self._graph_warm[name] = self._graph_warm.get(name, 0) + 1
-                scalars = {}
-                fn(*args, scalars)
-                return scalars
+                return None
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             scalars = {}
@@ -588,29 +609,16 @@ class Trainer:
             try:
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     fn(*args, scalars)
+                self._graphs[name] = (g, scalars)
             except Exception as e:  # keep training: this body runs eagerly from now on
                 import warnings
                 torch.cuda.synchronize()
                 warnings.warn(f"hipGraph capture of '{name}' failed ({type(e).__name__}: {e}); running it eagerly")
                 self._graphs[name] = None
-                if gc_was_enabled:
-                    gc.enable()
-                scalars = {}
-                fn(*args, scalars)
-                return scalars
             finally:
                 if gc_was_enabled:
                     gc.enable()
-            self._graphs[name] = (g, scalars)
-        if self._graphs[name] is None:
-            scalars = {}
-            fn(*args, scalars)
-            return scalars
-        g, scalars = self._graphs[name]
-        g.replay()
-        if os.environ.get("DGV2_GRAPH_SYNC"):  # debugging aid: serialise host and device after each replay
-            torch.cuda.synchronize()
-        return scalars
+        return self._graphs[name]
 
     def _link_graphs(self, head, tail):
         """The tail of a split body needs the autograd graph its head built: if either capture failed, both run
@@ -628,213 +636,207 @@ class Trainer:
             opt.step()
 
     # ------------------------------------------------------------------ one iteration
+    # step() lists the sub-steps.  What varies between one process, several chunks and several ranks is decided once, in
+    # _plan; how a gradient is exchanged and applied is written once, in _reduce_start / _reduce_finish.
+    def _plan(self, iteration):
+        nacc, dist = self.num_accumulation, parallel.is_dist()
+        fused = not dist and nacc == 1 and os.environ.get("DGV2_NO_FUSED_OPT") is None
+        rccl_graphs = dist and self.use_graphs and self.device.type == "cuda" and torch.distributed.get_backend() == "nccl"
+        return StepPlan(
+            nacc=nacc, dist=dist, fused=fused, split_d=self.split_d, fuse_d=fused and not self.split_d,
+            fold=rccl_graphs and os.environ.get("DGV2_NO_FOLDED_REDUCE") is None,
+            late_reals=nacc == 1 and not self.use_real_in_g, part_rest="rest" if self.split_d else None,
+            captured_tail=rccl_graphs and nacc == 1, ada_due=iteration % self.lazy_ada == 0,
+            r1_due=self.gp_weight > 0.0 and iteration % self.lazy_gp == 0,
+            pl_due=self.pl_weight > 0.0 and iteration % self.lazy_pl == 0)
+
     def _acc_name(self, name, j):
         # chunk 0 overwrites the flat gradient buffer, later chunks add to it: two different captured bodies
         return name if j == 0 else name + "/acc"
 
-    def _fold(self):
-        # fold: the small reductions ride INSIDE the optimizer graphs (G's 17.5 MB, D's 20 MB "rest", R1's) -- every graph
-        # launch and every cross-stream join costs the GPU a dependency bubble (one rank on RCCL: 8 graphs + 3 joins per
-        # iteration ran 3.6 % behind the 4-graph plain step); only D's head reduction (134 MB under the trunk's backward)
-        # keeps its side stream.  Eager / gloo runs keep the asynchronous form.
-        return (parallel.is_dist() and self.use_graphs and self.device.type == "cuda"
-                and torch.distributed.get_backend() == "nccl" and os.environ.get("DGV2_NO_FOLDED_REDUCE") is None)
-
-    def _g_substep(self, iteration, nacc, late_reals, log, real):
-        """The G step in its exchanging / accumulating form: bodies, gradient reduction, optimizer step."""
-        for j in gradient_accumulation(nacc, parallel.is_dist(), self.ddp_models):
-            if j == 0 and not self._g_bufs_synced:
+    def _chunks(self, p):
+        """The chunk indices of a sub-step that runs G's forward: a rank's share of the global batch, chunk by chunk
+        (reference: trainer.py:253-257; under gans.context_manager.gradient_accumulation like the reference's loops: every
+        chunk but the last inside the exchangers' no_sync, which would suppress an exchange issued from inside a body).
+        DDP(broadcast_buffers=True) re-broadcasts rank 0's buffers before a forward of the wrapped G whenever the
+        PREVIOUS forward ran with grad mode on and outside `no_sync` (torch DDP: require_forward_param_sync).  The
+        reference's D step calls G with grad mode on (trainer.py:379, only requires_grad is off), so both G forwards
+        of an iteration are preceded by a broadcast -- between the two this rank's forward has moved ema_var / w_avg,
+        the second one is not redundant -- while the later chunks of an accumulation loop (their predecessors ran
+        under no_sync) are not.  Exactly that is kept.
+        Where the broadcast travels: the one before the G step rode in the previous iteration's tail exchange
+        (_g_bufs_synced), the one before the D step rides behind G's gradients; the stand-alone sync_buffers remains
+        for the first iteration and around the path-length step."""
+        for j in gradient_accumulation(p.nacc, p.dist, self.ddp_models):
+            if p.dist and j == 0 and not self._g_bufs_synced:
                 parallel.sync_buffers(self.G)
-            if self.use_real_in_g:
-                log(self._run(self._acc_name("g_fb", j), self.g_fb_rel, real(j), j))
-            else:
-                log(self._run(self._acc_name("g_fb", j), self.g_fb, j))
-        # G's 17.5 MB (+ rank 0's buffers) leave on the communication stream; the real batch of this iteration is
-        # fetched / generated and converted meanwhile (the D step itself starts with a forward of the UPDATED G)
-        fold = self._fold()
+            yield j
 
-        def g_reduce_opt(sc):
-            self.g_sync.all_reduce(carry=True)
-            self._opt_step(self.optim_G)
+    def _real(self, j):
+        if self._reals is not None:
+            self.x_real.copy_(self._reals[j])
+        return self.x_real
 
-        if fold:
-            if late_reals:
-                self.fetch_reals(next(self.iter_train_loader), out=self.x_real)
-            # (its own body name: "g_opt" is the Adam-only graph of the non-folded form and of the path-length step)
-            ok = self.g_sync.carry_ok()   # outside the graph: a replay carries what it carried at capture time
-            self._run("g_red_opt", g_reduce_opt)
-            self._g_bufs_synced = ok and self.g_sync.last_carried
+    def _chunk(self, p, name, fn, *args):
+        """_run a body whose scalars are logged, one entry per chunk."""
+        for k, v in self._run(name, fn, *args).items():
+            # under graph replay the body's scalar tensors are static buffers: keep a copy per chunk
+            self._per_chunk[k].append(v.clone() if p.nacc > 1 else v)
+
+    # "Reduce this exchanger's gradient, then Adam", in two halves (D and R1 put other work between them) and three forms:
+    #   "none"   one process, one chunk: body and Adam were ONE body (see _fb_opt), nothing is left to do
+    #   "fold"   the reduction rides INSIDE the optimizer graph (G's 17.5 MB, D's 20 MB "rest", R1's): every graph launch
+    #            and every cross-stream join costs the GPU a dependency bubble (one rank on RCCL: 8 graphs + 3 joins per
+    #            iteration ran 3.6 % behind the 4-graph plain step).  RCCL + graphs only (StepPlan.fold)
+    #   "async"  the reduction starts on the communication stream (captured: the side stream), the caller's work runs
+    #            under it, the finish half joins it and runs Adam alone.  Eager / gloo runs, and in every run D's head
+    #            reduction (134 MB under the trunk's backward) and the path-length step
+    def _reduce_start(self, form, sync, part=None, carry=False):
+        if form != "async":
+            return
+        ok = carry and sync.carry_ok()
+        h = sync.all_reduce_captured(part=part, carry=carry)
+        self._in_flight.append((sync, h))
+        if carry:
+            self._carry_landed = h is not None and ok
+
+    def _reduce_join(self):
+        for sync, h in self._in_flight:
+            sync.wait(h)
+        self._in_flight = []
+
+    def _reduce_finish(self, form, sync, opt, name, fold_name=None, part=None, carry=False):
+        """carry (G's exchanger): rank 0's mutable buffers ride behind the gradients; whether they arrived on every rank
+        is written to _g_bufs_synced.  fold_name: the folded body's name where it is another graph than `name` (Adam only)."""
+        self._reduce_join()
+        if form == "none":
+            return
+        if form == "fold":
+            # outside the graph: a replay carries what it carried at capture time
+            self._carry_landed = carry and sync.carry_ok()
+            self._run(fold_name or name, self._reduce_opt, sync, part, carry, opt)
         else:
-            ok = self.g_sync.carry_ok()
-            h = self.g_sync.all_reduce_captured(carry=True)
-            if late_reals:
-                self.fetch_reals(next(self.iter_train_loader), out=self.x_real)
-            self.g_sync.wait(h)
-            self._g_bufs_synced = h is not None and ok and self.g_sync.last_carried
-            self._run("g_opt", lambda sc: self._opt_step(self.optim_G))
+            self._run(name, self._reduce_opt, None, part, carry, opt)
+        if carry:
+            self._g_bufs_synced = self._carry_landed and sync.last_carried
 
+    def _reduce_opt(self, sync, part, carry, opt, scalars):
+        if sync is not None:     # (None: the reduction ran on the communication stream, this body is Adam alone)
+            sync.all_reduce(part=part, carry=carry)
+        self._opt_step(opt)
 
-    def step(self, iteration):
-        self.G.train()
-        self.set_warmup_params(iteration)
-        nacc = self.num_accumulation
-        per_chunk = defaultdict(list)
-
-        def log(sc):
-            for k, v in sc.items():
-                # under graph replay the body's scalar tensors are static buffers: keep a copy per chunk
-                per_chunk[k].append(v.clone() if nacc > 1 else v)
-
-        # a rank's share of the global batch, chunk by chunk (reference: trainer.py:253-257; the loops below run under
-        # gans.context_manager.gradient_accumulation like the reference's: every chunk but the last inside the
-        # gradient exchangers' no_sync, so that an exchange issued from inside a body would be suppressed there).  With one chunk and an
-        # objective whose G step does not look at reals, the batch is prepared AFTER the G step's backward: it is the one
-        # piece of work on this rank that does not depend on G's reduced gradient, so G's all-reduce runs under it.
-        late_reals = nacc == 1 and not self.use_real_in_g
-        reals = None
-        if nacc > 1:
-            reals = [self.fetch_reals(next(self.iter_train_loader))["image"] for _ in range(nacc)]
-        elif not late_reals:
+    def _g_step(self, p):
+        fb = self.g_fb_rel if self.use_real_in_g else self.g_fb
+        if p.fused:
+            self._chunk(p, "g_step", self._fb_opt, fb, self.optim_G, *((self._real(0), 0) if self.use_real_in_g else (0,)))
+        else:
+            for j in self._chunks(p):
+                self._chunk(p, self._acc_name("g_fb", j), fb, *((self._real(j), j) if self.use_real_in_g else (j,)))
+        # G's 17.5 MB (+ rank 0's buffers) leave on the communication stream.  With one chunk and an objective whose G
+        # step does not look at reals, the real batch is fetched / generated and converted meanwhile: the one piece of
+        # work on this rank that does not depend on G's reduced gradient (the D step starts with a forward of the UPDATED G)
+        self._reduce_start(p.g_exchange, self.g_sync, carry=True)
+        if p.late_reals:
             self.fetch_reals(next(self.iter_train_loader), out=self.x_real)
+        # ("g_red_opt": "g_opt" is the Adam-only graph of the asynchronous form and of the path-length step)
+        self._reduce_finish(p.g_exchange, self.g_sync, self.optim_G, "g_opt", fold_name="g_red_opt", carry=True)
 
-        def real(j):
-            if nacc > 1:
-                self.x_real.copy_(reals[j])
-            return self.x_real
+    def _pl_step(self, p):
+        for j in self._chunks(p):
+            self._chunk(p, self._acc_name("pl_fb", j), self.pl_fb, j)
+        self._reduce_start("async", self.g_sync, carry=True)
+        self._reduce_finish("async", self.g_sync, self.optim_G, "g_opt", carry=True)
 
-        # DDP(broadcast_buffers=True) re-broadcasts rank 0's buffers before a forward of the wrapped G whenever the
-        # PREVIOUS forward ran with grad mode on and outside `no_sync` (torch DDP: require_forward_param_sync).  The
-        # reference's D step calls G with grad mode on (trainer.py:379, only requires_grad is off), so both G forwards
-        # of an iteration are preceded by a broadcast -- between the two this rank's forward has moved ema_var / w_avg,
-        # the second one is not redundant -- while the later chunks of an accumulation loop (their predecessors ran
-        # under no_sync) are not.  Exactly that is kept.
-        # Where the broadcast travels: the one before the G step rode in the previous iteration's tail exchange
-        # (_g_bufs_synced), the one before the D step rides behind G's gradients; the stand-alone sync_buffers remains
-        # for the first iteration and around the path-length step.
-        # one process, one chunk: forward / backward and optimizer step of a sub-step are ONE body (see g_fb_opt)
-        fuse_opt = (not parallel.is_dist()) and nacc == 1 and os.environ.get("DGV2_NO_FUSED_OPT") is None
-        if fuse_opt:
-            if self.use_real_in_g:
-                log(self._run("g_step", self.g_fb_rel_opt, real(0), 0))
-            else:
-                log(self._run("g_step", self.g_fb_opt, 0))
-                self.fetch_reals(next(self.iter_train_loader), out=self.x_real)
-            fold = False
-        else:
-            self._g_substep(iteration, nacc, late_reals, log, real)
-            fold = self._fold()
-
-        if self.pl_weight > 0.0 and iteration % self.lazy_pl == 0:
-            for j in gradient_accumulation(nacc, parallel.is_dist(), self.ddp_models):
-                if j == 0 and not self._g_bufs_synced:
-                    parallel.sync_buffers(self.G)
-                log(self._run(self._acc_name("pl_fb", j), self.pl_fb, j))
-            ok = self.g_sync.carry_ok()
-            h = self.g_sync.all_reduce_captured(carry=True)
-            self.g_sync.wait(h)
-            self._g_bufs_synced = h is not None and ok and self.g_sync.last_carried
-            self._run("g_opt", lambda sc: self._opt_step(self.optim_G))   # Adam only: the reduction ran just above
-
-        fuse_d = fuse_opt and not self.split_d
-        pending = []
-        for j in gradient_accumulation(nacc, parallel.is_dist(), self.ddp_models):
-            if fuse_d:
-                log(self._run("d_step", self.d_fb_opt, real(j), j))
-                continue
-            if j == 0 and not self._g_bufs_synced:
-                parallel.sync_buffers(self.G)
-            if self.split_d:
+    def _d_step(self, p):
+        """D's bodies and the start of its reductions; step() finishes them behind the EMA update."""
+        for j in self._chunks(p):
+            if p.fuse_d:
+                self._chunk(p, "d_step", self._fb_opt, self.d_fb, self.optim_D, self._real(j), j)
+            elif p.split_d:
                 head, tail = self._acc_name("d_fb_head", j), self._acc_name("d_fb_tail", j)
-                log(self._run(head, self.d_fb_head, real(j), j))
-                if j == nacc - 1:
+                self._chunk(p, head, self.d_fb_head, self._real(j), j)
+                if j == p.nacc - 1:
                     # 134 of D's 154 MB leave now, on the communication stream, under the trunk's backward
-                    pending.append(self.d_sync.all_reduce_captured(part="first"))
+                    self._reduce_start("async", self.d_sync, part="first")
                 self._run(tail, self.d_fb_tail, j)
                 self._link_graphs(head, tail)
             else:
-                log(self._run(self._acc_name("d_fb", j), self.d_fb, real(j), j))
-        # the (rest of the) gradient reduction of D runs on the communication stream while the EMA generator is updated
-        # (G is final for this iteration: nothing below touches it)
-        rest = "rest" if self.split_d else None
-        if not fold and not fuse_d:
-            pending.append(self.d_sync.all_reduce_captured(part=rest))
-        decay = self.ema_decay(iteration)
-        ema_inplace(self.G_ema, self.G, decay)
-        for h in pending:
-            self.d_sync.wait(h)
+                self._chunk(p, self._acc_name("d_fb", j), self.d_fb, self._real(j), j)
+        self._reduce_start(p.d_exchange, self.d_sync, part=p.part_rest)
 
-        def d_reduce_opt(part):
-            def body(sc):
-                self.d_sync.all_reduce(part=part)
-                self._opt_step(self.optim_D)
-            return body
+    def _r1_step(self, p):
+        """lazy R1's bodies and the start of its reduction; step() applies it behind the tail exchange."""
+        for j in gradient_accumulation(p.nacc, p.dist, self.ddp_models):
+            if p.fuse_d:
+                self._chunk(p, "r1_step", self._fb_opt, self.r1_fb, self.optim_D, self._real(j), j)
+            else:
+                self._chunk(p, self._acc_name("r1_fb", j), self.r1_fb, self._real(j), j)
+        # R1's 154 MB leave asynchronously; the scalar bookkeeping runs under them.  The optimizer step cannot move
+        # past the next iteration's G step, whose D forward must see the regularised weights (trainer.py:419-451).
+        self._reduce_start(p.d_exchange, self.d_sync)
 
-        if fuse_d:
-            pass                               # the optimizer step rode in the body
-        elif fold:
-            self._run("d_opt", d_reduce_opt(rest))
-        else:
-            self._run("d_opt", lambda sc: self._opt_step(self.optim_D))
-        self._d_bank_fresh = False
+    def _tail_body(self, scalars, ada_due, out):
+        res, ada_stats = parallel.tail_exchange(scalars, self.A.stats() if ada_due else None, self.G)
+        if ada_due:
+            res["stats/ada_rt"] = self.A.update_p(stats=ada_stats).reshape(())
+            res["stats/ada_p"] = self.A.p.detach().clone()
+        out.update(res)
 
-        self._g_bufs_synced = False   # the D step's G forward moved this rank's ema_var / w_avg again
-        r1_pending = None
-        if self.gp_weight > 0.0 and iteration % self.lazy_gp == 0:
-            for j in gradient_accumulation(nacc, parallel.is_dist(), self.ddp_models):
-                if fuse_d:
-                    log(self._run("r1_step", self.r1_fb_opt, real(j), j))
-                else:
-                    log(self._run(self._acc_name("r1_fb", j), self.r1_fb, real(j), j))
-            # R1's 154 MB leave asynchronously; the scalar bookkeeping below runs under them.  The optimizer step cannot
-            # move past the next iteration's G step, whose D forward must see the regularised weights (trainer.py:419-451).
-            if not fold and not fuse_d:
-                r1_pending = self.d_sync.all_reduce_captured()
-
-        scalars = {k: (v[0] if len(v) == 1 else torch.stack([t.reshape(()) for t in v]).mean())
-                   for k, v in per_chunk.items()}          # mean over the chunks (reference: trainer.py:471-476)
-        # ONE small collective closes the iteration: the logged scalars, ADA's statistic pair when its update is due
-        # (adaptive_augment.py:372-384) and rank 0's G buffers for the next iteration's first forward
-        ada_due = iteration % self.lazy_ada == 0
-
-        def tail(sc):
-            res, ada_stats = parallel.tail_exchange(scalars, self.A.stats() if ada_due else None, self.G)
-            if ada_due:
-                res["stats/ada_rt"] = self.A.update_p(stats=ada_stats).reshape(())
-                res["stats/ada_p"] = self.A.p.detach().clone()
-            sc.update(res)
-
-        # One communicator, one order: the tail exchange below is a second collective of the SAME RCCL communicator,
-        # issued from the main stream (as a graph replay) or from c10d's stream (eager) -- neither is ordered against
-        # a reduction replaying on the side stream, and two unordered collectives of one communicator can interleave
+    def _tail(self, p, scalars):
+        """ONE small collective closes the iteration: the logged scalars, ADA's statistic pair when its update is due
+        (adaptive_augment.py:372-384) and rank 0's G buffers for the next iteration's first forward."""
+        # One communicator, one order: the tail exchange is a second collective of the SAME RCCL communicator, issued
+        # from the main stream (as a graph replay) or from c10d's stream (eager) -- neither is ordered against a
+        # reduction replaying on the side stream (R1's), and two unordered collectives of one communicator can interleave
         # differently per rank (hang / corrupted buffers).  Join the reduction first (parallel._side_stream's invariant).
-        if r1_pending is not None:
-            self.d_sync.wait(r1_pending)
-            r1_pending = None
-        gp_key = "loss/D/gradient_penalty"
-        captured_tail = (parallel.is_dist() and nacc == 1 and self.use_graphs and self.device.type == "cuda"
-                         and torch.distributed.get_backend() == "nccl")
-        if captured_tail:
+        self._reduce_join()
+        if p.captured_tail:
             # The packing, the collective and the unpacking replay as a hipGraph too; its inputs are the bodies' static
             # scalar buffers.  Two variants only (ADA's update due or not): the R1 scalar, present every lazy.gp-th
             # iteration, travels EVERY iteration from a buffer of its own, so that no new key set -- i.e. no capture --
             # turns up deep into a run (a capture costs milliseconds; bench.py's timed region met one).
-            if gp_key in scalars:
-                self._gp_scalar.copy_(scalars[gp_key].reshape(()))
+            gp_key = "loss/D/gradient_penalty"
             had_gp = gp_key in scalars
-            scalars = dict(scalars)
-            scalars[gp_key] = self._gp_scalar
-            out = dict(self._run("tail" + ("/ada" if ada_due else ""), tail))
+            if had_gp:
+                self._gp_scalar.copy_(scalars[gp_key].reshape(()))
+            scalars = {**scalars, gp_key: self._gp_scalar}
+            out = dict(self._run("tail" + ("/ada" if p.ada_due else ""), self._tail_body, scalars, p.ada_due))
             if not had_gp:
                 out.pop(gp_key, None)
         else:
             out = {}
-            tail(out)
-        self._g_bufs_synced = parallel.is_dist()
-        if self.gp_weight > 0.0 and iteration % self.lazy_gp == 0 and not fuse_d:
-            if fold:   # (with the split D the plain step's optimizer graph reduces the "rest" segment only: another body)
-                self._run("d_opt" if rest is None else "d_all_opt", d_reduce_opt(None))
-            else:
-                self._run("d_opt", lambda sc: self._opt_step(self.optim_D))
+            self._tail_body(scalars, p.ada_due, out)
+        self._g_bufs_synced = p.dist
+        return out
+
+    def step(self, iteration):
+        self.G.train()
+        self.set_warmup_params(iteration)
+        p = self._plan(iteration)
+        self._per_chunk, self._in_flight, self._reals = defaultdict(list), [], None
+        if p.nacc > 1:
+            self._reals = [self.fetch_reals(next(self.iter_train_loader))["image"] for _ in range(p.nacc)]
+        elif not p.late_reals:
+            self.fetch_reals(next(self.iter_train_loader), out=self.x_real)
+        self._g_step(p)
+        if p.pl_due:
+            self._pl_step(p)
+        self._d_step(p)
+        # the (rest of the) gradient reduction of D runs on the communication stream while the EMA generator is updated
+        # (G is final for this iteration: nothing below touches it)
+        decay = self.ema_decay(iteration)
+        ema_inplace(self.G_ema, self.G, decay)
+        self._reduce_finish(p.d_exchange, self.d_sync, self.optim_D, "d_opt", part=p.part_rest)
+        self._d_bank_fresh = False
+        self._g_bufs_synced = False   # the D step's G forward moved this rank's ema_var / w_avg again
+        if p.r1_due:
+            self._r1_step(p)
+        scalars = {k: (v[0] if len(v) == 1 else torch.stack([t.reshape(()) for t in v]).mean())
+                   for k, v in self._per_chunk.items()}    # mean over the chunks (reference: trainer.py:471-476)
+        out = self._tail(p, scalars)
+        if p.r1_due:   # (with the split D the plain step's optimizer graph reduces the "rest" segment only: another body)
+            self._reduce_finish(p.d_exchange, self.d_sync, self.optim_D, "d_opt",
+                                fold_name="d_all_opt" if p.split_d else "d_opt")
         set_requires_grad(self.D, False)
 
         if self.sync_scalars:

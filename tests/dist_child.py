@@ -2,6 +2,8 @@
 cuda:0), or the single-process reference run on the concatenated batch.  Writes its final state to <out>/rank<r>.pt.
 
     python tests/dist_child.py <out_dir> <world> <rank> <port> <iterations> <hip_graph 0|1>
+
+DGV2_TEST_STEP_TRACE=1 installs tests/step_recorder.py and adds every iteration's event list to the saved state ("trace").
 """
 import os
 import sys
@@ -70,6 +72,10 @@ def main():
     torch.manual_seed(rank)    # different initial weights per rank on purpose: rank 0's must win (DDP ctor semantics)
     np.random.seed(rank)       # (the PE frequencies are drawn with numpy's generator)
     tr = Trainer(cfg, sync_scalars=False)
+    rec = None
+    if os.environ.get("DGV2_TEST_STEP_TRACE"):
+        import step_recorder
+        rec = step_recorder.install()
     if rank == 0:
         G0, D0 = build_models(cfg, "cpu")
         tr.G.load_state_dict(recipe.fill_state_dict(G0.state_dict(), 7))
@@ -84,17 +90,23 @@ def main():
         idx = torch.tensor([big_index(rank, j, world_total) for j in range(B_RANK)])
     else:
         idx = torch.arange(B_RANK * world_total)
-    scal = []
+    scal, trace = [], []
     for it in range(1, iters + 1):
         d, depth, mask = draws_for(it, world_total)
         tr.set_draws({k: v[idx] for k, v in d.items()})
         tr.iter_train_loader = iter([{"depth": depth[idx].cuda(), "mask": mask[idx].cuda()}])
+        if rec is not None:
+            rec.take()     # (what happened between two steps -- the broadcasts above -- is not the iteration's)
         out = tr.step(it)
+        if rec is not None:
+            trace.append(rec.take())
         scal.append({k: float(v) for k, v in out.items()})
     state = {"G": tr.G.state_dict(), "D": tr.D.state_dict(), "G_ema": tr.G_ema.state_dict(), "p": tr.A.p, "scalars": scal,
              "optD_v": [tr.optim_D.state[p]["exp_avg_sq"] for p in tr.D.parameters()],
              "graphs": sorted(k for k, v in tr._graphs.items() if v is not None),
              "backend": dist.get_backend() if dist.is_initialized() else None, "split_d": bool(tr.split_d)}
+    if rec is not None:
+        state["trace"] = trace
     state = {k: ({a: b.detach().cpu() for a, b in v.items()} if isinstance(v, dict) else
                  ([t.detach().cpu() for t in v] if k == "optD_v" else (v.detach().cpu() if torch.is_tensor(v) else v)))
              for k, v in state.items()}

@@ -36,6 +36,26 @@ def _run(out, world, iters, graph, env_extra=None):
     return [torch.load(os.path.join(out, f"rank{r}_of{world}.pt"), weights_only=False) for r in range(world)]
 
 
+def _assert_same_run(one, other, first_to_rounding=False):
+    """`other` (saved state of a dist_child) ran what the one-process run `one` ran: every scalar of every iteration to
+    5e-3, at most 2e-3 of the elements of G, D and G_ema off by more than 1e-3 of their tensor's largest; with
+    first_to_rounding the scalars of iteration 1 (the same kernels on the same numbers) to 1e-5."""
+    if first_to_rounding:
+        for k in one["scalars"][0]:
+            a, b = one["scalars"][0][k], other["scalars"][0][k]
+            assert abs(a - b) <= 1e-5 * abs(a) + 1e-7, ("iteration 1", k, a, b)
+    for it, (a, b) in enumerate(zip(one["scalars"], other["scalars"]), 1):
+        for k in a:
+            assert abs(a[k] - b[k]) <= 5e-3 * abs(a[k]) + 1e-4, (it, k, a[k], b[k])
+    for key in ("G", "D", "G_ema"):
+        bad = tot = 0
+        for k, v in one[key].items():
+            err = (v.float() - other[key][k].float()).abs()
+            bad += int((err > 1e-3 * float(v.abs().max()) + 1e-6).sum())
+            tot += v.numel()
+        assert bad <= 2e-3 * tot, (key, bad, tot)
+
+
 @pytest.mark.parametrize("graph", [False, True])
 def test_two_ranks_identical_and_equal_to_one_process(tmp_path, graph):
     iters = 8 if graph else 4     # with hipGraphs iterations 1-2 warm up, 3 captures, later ones replay (R1: 2, 4 | 6, 8)
@@ -57,16 +77,7 @@ def test_two_ranks_identical_and_equal_to_one_process(tmp_path, graph):
     # ranks see different samples: their local losses differ, the logged (all-reduced) scalars do not
     assert r0["scalars"] == r1["scalars"]
     (one,) = _run(tmp_path, 1, iters, graph, {"DGV2_TEST_WORLD_TOTAL": "2"})
-    for it, (a, b) in enumerate(zip(one["scalars"], r0["scalars"]), 1):
-        for k in a:
-            assert abs(a[k] - b[k]) <= 5e-3 * abs(a[k]) + 1e-4, (it, k, a[k], b[k])
-    for key in ("G", "D", "G_ema"):
-        bad = tot = 0
-        for k, v in one[key].items():
-            err = (v.float() - r0[key][k].float()).abs()
-            bad += int((err > 1e-3 * float(v.abs().max()) + 1e-6).sum())
-            tot += v.numel()
-        assert bad <= 2e-3 * tot, (key, bad, tot)
+    _assert_same_run(one, r0)
 
 
 @pytest.mark.parametrize("graph", [False, True])
@@ -86,16 +97,4 @@ def test_one_rank_on_rccl_equals_the_plain_run(tmp_path, graph):
         assert {"g_fb/inj", "g_red_opt", "d_fb_head/inj", "d_fb_tail/inj", "d_opt", "r1_fb/inj"} <= set(r["graphs"]), r["graphs"]
     (one,) = _run(tmp_path / "plain", 1, iters, graph)
     assert one["backend"] is None
-    for k in one["scalars"][0]:
-        a, b = one["scalars"][0][k], r["scalars"][0][k]
-        assert abs(a - b) <= 1e-5 * abs(a) + 1e-7, ("iteration 1", k, a, b)
-    for it, (a, b) in enumerate(zip(one["scalars"], r["scalars"]), 1):
-        for k in a:
-            assert abs(a[k] - b[k]) <= 5e-3 * abs(a[k]) + 1e-4, (it, k, a[k], b[k])
-    for key in ("G", "D", "G_ema"):
-        bad = tot = 0
-        for k, v in one[key].items():
-            err = (v.float() - r[key][k].float()).abs()
-            bad += int((err > 1e-3 * float(v.abs().max()) + 1e-6).sum())
-            tot += v.numel()
-        assert bad <= 2e-3 * tot, (key, bad, tot)
+    _assert_same_run(one, r, first_to_rounding=True)

@@ -326,6 +326,56 @@ def test_full_size_bf16_graph_replay_equals_eager():
         assert g_frac <= max(3 * n_frac + 1e-4, 2e-2), (name, g_frac, n_frac)
 
 
+# ---------------------------------------------------------------------------- the non-fused bodies
+@pytest.mark.parametrize("hip_graph", [False, True])
+def test_non_fused_bodies_equal_the_fused_step(hip_graph, monkeypatch):
+    """One process, one chunk runs g_step / d_step / r1_step (body + Adam in one); every distributed or accumulating
+    run uses g_fb + g_opt, d_fb + d_opt, r1_fb + d_opt instead.  DGV2_NO_FUSED_OPT (read per step) selects the latter
+    on one GPU: the fixture's iterations from the same state, draws and reals must give the same run, eagerly and as
+    replays.  Criteria of test_full_size_bf16_graph_replay_equals_eager ("same run, other body split"): what precedes
+    the first optimizer step agrees to 1e-6; later scalars and the final states are measured against a second run of
+    the plain trainer (float atomics through Adam with beta1 = 0), with that test's floors."""
+    d = _load_trainer_fixture()
+    tag = "t."
+    plain, hp, sdG, sdD = _fixture_trainer(d, tag, hip_graph)
+    other, _, _, _ = _fixture_trainer(d, tag, hip_graph)
+    n = hp["iterations"]
+
+    def run(tr, its):
+        if tr is other:
+            monkeypatch.setenv("DGV2_NO_FUSED_OPT", "1")
+        else:
+            monkeypatch.delenv("DGV2_NO_FUSED_OPT", raising=False)
+        _reset(tr, hp, sdG, sdD)
+        return [{k: float(v) for k, v in _run_fixture_iteration(tr, d, tag, it, n).items()} for it in its]
+
+    state = lambda tr: {name: copy.deepcopy(m.state_dict()) for name, m in (("G", tr.G), ("D", tr.D), ("Gema", tr.G_ema))}
+    if hip_graph:
+        for tr in (plain, other):
+            run(tr, range(1, 7))     # two eager warm runs + capture of every body (R1 runs on even iterations)
+            assert all(tr.graphs_live().values()), tr.graphs_live()
+        assert set(plain._graphs) == {"g_step/inj", "d_step/inj", "r1_step/inj"}
+        assert set(other._graphs) == {"g_fb/inj", "g_opt", "d_fb/inj", "d_opt", "r1_fb/inj"}
+    e1 = run(plain, range(1, n + 1))
+    state_first = state(plain)
+    e2 = run(plain, range(1, n + 1))
+    nf = run(other, range(1, n + 1))
+    assert all(set(a) == set(b) for a, b in zip(e2, nf))
+    for k in ("loss/G/adversarial", "loss/D/output/real"):
+        assert abs(e2[0][k] - nf[0][k]) <= 1e-6 * abs(e2[0][k]), ("iteration 1", k, e2[0][k], nf[0][k])
+    worst = lambda a, b: max(abs(a[k] - b[k]) / (abs(a[k]) + 1e-3) for k in a)
+    noise = max(worst(a, b) for a, b in zip(e1, e2))
+    dev = max(worst(a, b) for a, b in zip(e2, nf))
+    print(f"non-fused vs fused scalars: deviation {dev:.3e}, plain-vs-plain noise {noise:.3e}")
+    assert dev <= max(3 * noise + 1e-4, 4e-2), (dev, noise)
+    s_plain, s_other = state(plain), state(other)
+    for name in ("G", "D", "Gema"):
+        n_frac = _state_mismatch(state_first[name], s_plain[name])
+        o_frac = _state_mismatch(s_plain[name], s_other[name])
+        print(f"non-fused vs fused {name}: mismatch fraction {o_frac:.3e}, plain-vs-plain {n_frac:.3e}")
+        assert o_frac <= max(3 * n_frac + 1e-4, 2e-2), (name, o_frac, n_frac)
+
+
 # ---------------------------------------------------------------------------- gradient accumulation
 @pytest.mark.parametrize("hip_graph", [False, True])
 def test_gradient_accumulation_equals_the_mean_of_the_chunks(hip_graph):
