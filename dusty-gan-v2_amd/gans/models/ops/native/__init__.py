@@ -15,7 +15,7 @@ scripts read and set it as <module>.<FLAG>.  Everything in a submodule's __all__
 """
 import dgv2_native as N  # noqa: F401  (native.N: the ctypes binding)
 from . import (act_resample, conv, crf, fourier, fp8, frame, glin, inversion, kitti, knn, loss, modgemm, modlayer,  # noqa: F401
-               modup, optim, rng, second_order, stem_tail_ada)
+               modup, optim, rng, second_order, segloss, stem_tail_ada)
 from .act_resample import *  # noqa: F401,F403
 from .fourier import *  # noqa: F401,F403
 from .glin import *  # noqa: F401,F403
@@ -34,3 +34,4 @@ from .rng import *  # noqa: F401,F403
 from .frame import *  # noqa: F401,F403
 from .crf import *  # noqa: F401,F403
 from .knn import *  # noqa: F401,F403
+from .segloss import *  # noqa: F401,F403

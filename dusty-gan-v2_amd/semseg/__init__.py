@@ -1,2 +1,4 @@
-"""Range-image segmentation side of the project (reference: semseg/): the CRF-RNN refinement layer and the kNN label
-filter on native kernels (semseg.models), and the confusion counts / IoU scoring of an evaluation (semseg.metrics)."""
+"""Range-image segmentation side of the project (reference: semseg/): the CRF-RNN refinement layer, the kNN label
+filter and the training objective -- focal loss under the masked mean, with the step's predictions and training
+confusion counts -- on native kernels (semseg.models), and the confusion counts / IoU scoring of an evaluation
+(semseg.metrics)."""

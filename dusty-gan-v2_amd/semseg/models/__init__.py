@@ -1,4 +1,5 @@
 from .crf_as_rnn import CRFRNN  # noqa: F401
 from .knn import kNN2d  # noqa: F401
+from .loss import FocalLoss, MaskedSegLoss  # noqa: F401
 
-__all__ = ["CRFRNN", "kNN2d"]
+__all__ = ["CRFRNN", "kNN2d", "FocalLoss", "MaskedSegLoss"]

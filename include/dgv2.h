@@ -29,6 +29,7 @@ extern "C" {
 #define DGV2_F32 0
 #define DGV2_BF16 1
 #define DGV2_FP8 2 /* OCP e4m3fn bytes; only where an entry says so (the *_fp8 / *_q8 entries) */
+#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits) */
 #define DGV2_EINVAL (-1)
 #define DGV2_ENOTSUP (-3) /* valid request that this build's kernels do not cover: use the documented fallback */
 
@@ -1152,6 +1153,56 @@ int dgv2_knn2d(int64_t* out, const float* depth, const int64_t* label, const flo
  * 1 <= num_classes <= 32, 1 <= n < 2^40; DGV2_EINVAL otherwise and for null conf / label / pred. */
 int dgv2_seg_confusion(int64_t* conf, const int64_t* label, const int64_t* pred, const float* mask, int64_t n,
                        int num_classes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * training objective of the range-image segmentation models (segloss.hip; semseg/models/loss.py here)
+ * replaces: FocalLoss.forward, semseg/models/loss.py:13-21 (cross_entropy + softmax + gather + pow + mul), under
+ *   masked_loss, train_semseg.py:194-197 (* mask, sum, mask.sum(), div), the argmax of its lines 270-273 and the
+ *   pred * mask, label * mask and masked sums of `evaluate` of its lines 290-296 -- and autograd through all of it.
+ * logit [B,C,H,W] NCHW contiguous of `dtype` (DGV2_F32, DGV2_BF16 or DGV2_F16), label int64 [B,H,W], mask fp32
+ * [B,H,W] or NULL (= 1 everywhere), alpha fp32 [C] or NULL (= 1 for every class).  All arithmetic in fp32, whatever
+ * the dtype.  Per pixel q with logits z_0..z_{C-1}, label y, mask m, class weights a_c:
+ *   p_c     = softmax(z)_c                    (max-subtracted)
+ *   lp      = log p_y                         (= z_y - max - log sum exp(z - max))
+ *   w       = (1 - p_y)^gamma                 (gamma == 0: w = 1 exactly, also where p_y == 1; 1 - p_y is taken as
+ *                                              sum_{c != y} exp(z_c - max) / sum_c exp(z_c - max): no cancellation)
+ *   L(q)    = -a_y w lp
+ *   loss    = sum_q m(q) L(q) / sum_q m(q)    (sum m == 0: 0 / 0 = NaN, as the reference)
+ *   dL/dz_j = a_y (delta_jy - p_j) (gamma p_y (1 - p_y)^(gamma-1) lp - (1 - p_y)^gamma)
+ *             (gamma == 0: a_y (p_j - delta_jy), plain weighted cross-entropy)
+ *   g_z(q)_j = gout m(q) / sum m * dL/dz_j    (per_pixel: gout(q) dL/dz_j, no mask, no sum)
+ * gamma == 0 or gamma >= 1: for 0 < gamma < 1 the reference's own gradient is NaN wherever p_y rounds to 1.
+ * A label outside [0, C) has L = 0 and a zero gradient, and its mask weight still counts in sum m (the reference raises
+ * or device-asserts there; this is the definition here).  The mask is a float WEIGHT for the loss and a FLAG for pred /
+ * conf: mask == 0 there means "count as class 0", any other value 1 -- the rule of dgv2_seg_confusion.
+ * pred(q) = lowest index among the largest logits (compared in the logits' own dtype; unspecified where a logit is
+ * NaN, and the loss is NaN there), times (m != 0).  conf int64 [C+1,C+1] is ACCUMULATED INTO: conf[row(label (m != 0)), col(pred)] += 1 with
+ * the rows / columns of dgv2_seg_confusion; integer atomics only, per block in LDS first.
+ *
+ * dgv2_seg_loss_forward.  Outputs, each NULL when not wanted (at least one is): loss_map fp32 [B,H,W] = L(q), unmasked
+ * (the reference's reduction="none"); pred int64 [B,H,W]; conf; sums fp32 [3] = {loss, sum m L, sum m}.  ONE launch does
+ * the per-pixel work; with `sums` a SECOND launch of one block folds the blocks' partial sums, which the first left in
+ * `scratch` (fp32, >= dgv2_seg_loss_scratch elements; required with sums), in a fixed order and divides: no float
+ * atomics, bit-identical from run to run, and the same bits for bf16 / fp16 logits as for their fp32 cast.
+ * The logits are read from HBM once: C <= 8 holds a pixel's C values in registers; 8 < C <= 32 walks the class planes
+ * twice (three times in the backward), the re-reads served by the cache.  Each thread reads 4 consecutive pixels of a
+ * plane with one 16-byte (fp32) / 8-byte (half) load where every pointer is 16-byte aligned and H*W % 4 == 0, and
+ * element by element otherwise, with the same results.
+ * dgv2_seg_loss_backward.  ONE launch, no scratch, no atomics: g_logit [B,C,H,W] in the logits' dtype (fp32 rounded to
+ * nearest even), the softmax recomputed.  per_pixel == 0: gout is ONE device float (the loss's upstream gradient) and
+ * sums the forward's (sum m is read from sums[2] on the device: nothing is read on the host, the step stays
+ * capturable).  per_pixel == 1: gout fp32 [B,H,W] (the cotangent of loss_map); mask and sums are not read.
+ * DGV2_EINVAL, nothing launched: a null required pointer (logit, label; forward: every output null, or sums without
+ * enough scratch; backward: g_logit, gout, sums when per_pixel == 0), B, H or W < 1, C outside 1..32, another dtype,
+ * gamma outside {0} U [1, inf) (NaN included), B*H*W >= 2^40, per_pixel not 0 / 1.
+ * ------------------------------------------------------------------------- */
+int dgv2_seg_loss_scratch(int64_t* elems, int B, int H, int W);
+int dgv2_seg_loss_forward(float* loss_map, int64_t* pred, int64_t* conf, float* sums, float* scratch,
+                          int64_t scratch_elems, const void* logit, const int64_t* label, const float* mask,
+                          const float* alpha, int B, int C, int H, int W, float gamma, int dtype, void* stream);
+int dgv2_seg_loss_backward(void* g_logit, const void* logit, const int64_t* label, const float* mask,
+                           const float* alpha, const float* gout, const float* sums, int B, int C, int H, int W,
+                           float gamma, int dtype, int per_pixel, void* stream);
 
 #ifdef __cplusplus
 }
