@@ -246,12 +246,7 @@ __global__ __launch_bounds__(256) void bias_partial_reduce_kernel(float* __restr
 // scratch (optional, fp32 [scratch_elems >= 2048 * C]): with it the pass runs on up to 2048 blocks and the
 // per-block column sums are folded by a second kernel (no atomics, no zero fill of gb); without it <= 256 blocks
 // add their sums with fp32 atomics (same-address atomics would serialise a larger grid).
-extern "C" int dgv2_bias_act_bwd(void* gx, float* gb, const void* gy, const void* ref, int64_t rows, int C,
-                                 float alpha, float scale, float* scratch, int64_t scratch_elems, int dtype,
-                                 void* stream) {
-  return dgv2_bias_act_bwd_rs(gx, gb, gy, ref, rows, C, alpha, scale, nullptr, scratch, scratch_elems, dtype, stream);
-}
-
+// row_scale (optional, fp32 [C]): a per-channel factor on the STORED gx only; gb sums the unscaled values.
 extern "C" int dgv2_bias_act_bwd_rs(void* gx, float* gb, const void* gy, const void* ref, int64_t rows, int C,
                                     float alpha, float scale, const float* row_scale, float* scratch,
                                     int64_t scratch_elems, int dtype, void* stream) {

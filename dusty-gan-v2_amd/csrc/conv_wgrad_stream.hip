@@ -912,7 +912,7 @@ int ws_dispatch_geom(float* part, const void* gy, const void* x, const WSPlan& p
 
 }  // namespace
 
-// Number of fp32 elements of scratch dgv2_conv_wgrad_stream needs for this geometry (0 and DGV2_EINVAL when
+// Number of fp32 elements of scratch dgv2_conv_wgrad_stream_pl needs for this geometry (0 and DGV2_EINVAL when
 // the geometry is not supported).
 extern "C" int dgv2_conv_wgrad_stream_scratch(int64_t* elems, int B, int H, int W, int C, int O, int k, int stride,
                                               int pad, int dtype) {
@@ -936,18 +936,8 @@ extern "C" int dgv2_bmm_tn_stream_scratch(int64_t* elems, int B, int H, int W, i
   return 0;
 }
 
-extern "C" int dgv2_bmm_tn_stream(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
-                                  int B, int H, int W, int C, int O, int dtype, void* stream) {
-  return dgv2_bmm_tn_stream_x(gw, scratch, scratch_elems, gy, x, 0, B, H, W, C, O, dtype, stream);
-}
-
 // x_shared != 0: x is one image [H, W, C] contracted against every sample's gy (the batch-shared positional encoding:
-// gw[b, o, c] = sum_p gy[b, p, o] * pe[p, c]).
-extern "C" int dgv2_bmm_tn_stream_x(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
-                                    int x_shared, int B, int H, int W, int C, int O, int dtype, void* stream) {
-  return dgv2_bmm_tn_stream_ld(gw, 0, scratch, scratch_elems, gy, x, x_shared, B, H, W, C, O, dtype, stream);
-}
-
+// gw[b, o, c] = sum_p gy[b, p, o] * pe[p, c]); 0: x is [B, H, W, C], one image per sample.
 // ldo > 0: gw is [B, O, ldo] with ldo >= C (and a multiple of 4): the columns [0, C) of the caller's wider per-sample weight
 // gradient, written in place (offset the pointer for another first column); 0: contiguous [B, O, C].
 extern "C" int dgv2_bmm_tn_stream_ld(float* gw, int64_t ldo, float* scratch, int64_t scratch_elems, const void* gy,
@@ -972,13 +962,7 @@ extern "C" int dgv2_bmm_tn_stream_ld(float* gw, int64_t ldo, float* scratch, int
 
 // gw fp32 [O, k*k, C] (overwritten).  k in {1,3}, pad = (k-1)/2, stride in {1,2}, C and O multiples of the
 // 16-byte vector (8 bf16 / 4 fp32).  scratch: fp32 [scratch_elems] >= dgv2_conv_wgrad_stream_scratch(...).
-extern "C" int dgv2_conv_wgrad_stream(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
-                                      int B, int H, int W, int C, int O, int k, int stride, int pad, int ring,
-                                      int dtype, void* stream) {
-  return dgv2_conv_wgrad_stream_pl(gw, scratch, scratch_elems, gy, x, B, H, W, C, O, k, stride, pad, ring, 1.f, 0, dtype,
-                                   stream);
-}
-
+// scale: a factor on the whole gradient (1.f = none); param_layout != 0: gw in the parameter's own [O, C, k, k] layout.
 extern "C" int dgv2_conv_wgrad_stream_pl(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
                                          int B, int H, int W, int C, int O, int k, int stride, int pad, int ring,
                                          float scale, int param_layout, int dtype, void* stream) {

@@ -349,7 +349,7 @@ int64_t fm_band_bytes(int H, int W) { return 1024 * ((int64_t)H / FM_RS + 1 + W 
 
 }  // namespace
 
-// Band operands of dgv2_fir_same_mfma for one SAME-SIZE table set (sparse rows exactly as for dgv2_resample_tab): built
+// Band operands of dgv2_fir_same_mfma for one SAME-SIZE table set (sparse rows exactly as for dgv2_resample_tab_sq): built
 // once, kept by the caller next to the tables.  bands: device buffer of >= *bytes_needed bytes (a call with bands == NULL
 // only reports *bytes_needed).  Contract on the tables (a violation raises bit DGV2_STATUS_FIR_TABLE of the caller's device word *status):
 //   |idx_h[ho][a] - ho| <= 4,   (idx_w[wo][e] - wo + 8) mod W < 24,   every coefficient -- and every sum of the
@@ -370,7 +370,7 @@ extern "C" int dgv2_fir_same_mfma_prep(void* bands, int64_t bands_bytes, int64_t
 }
 
 // y = R x for a same-size separable resampling whose band operands dgv2_fir_same_mfma_prep built, bf16, x / y
-// [B, H, W, C] contiguous.  DGV2_ENOTSUP unless C % 32 == 0, H % 8 == 0, W % 32 == 0 (then: dgv2_resample_tab).
+// [B, H, W, C] contiguous.  DGV2_ENOTSUP unless C % 32 == 0, H % 8 == 0, W % 32 == 0 (then: dgv2_resample_tab_sq).
 extern "C" int dgv2_fir_same_mfma(void* y, const void* x, const void* bands, int B, int C, int H, int W, void* stream) {
   if (!y || !x || !bands) return DGV2_EINVAL;
   if (!fm_covers(B, C, H, W)) return DGV2_ENOTSUP;

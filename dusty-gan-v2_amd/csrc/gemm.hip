@@ -93,13 +93,6 @@ int launch_bmm_tn_cat(float* gw, const void* gy, const void* xa, const void* xs,
 
 }  // namespace
 
-extern "C" int dgv2_bmm_nn(void* y, const void* x, const void* w, int B, int P, int I, int O, int ldx, int ldy,
-                           int64_t wstride, const float* bias, int act, float alpha, float scale, int dtype,
-                           int ydtype, void* stream) {
-  return dgv2_bmm_nn_sq(y, x, w, B, P, I, O, ldx, ldy, wstride, nullptr, bias, act, alpha, scale, nullptr, dtype, ydtype,
-                        nullptr, 0, nullptr, stream);
-}
-
 extern "C" int dgv2_bmm_nn_sq(void* y, const void* x, const void* w, int B, int P, int I, int O, int ldx, int ldy,
                               int64_t wstride, const float* row_scale, const float* bias, int act, float alpha,
                               float scale, const void* resid, int dtype, int ydtype, float* sumsq, int sumsq_cap,
@@ -141,13 +134,6 @@ extern "C" int dgv2_bmm_tn(float* gw, const void* gy, const void* x, int B, int 
 // xa = FIR-upsampled previous activation (per sample), xs = PE of the UNSHIFTED angle grid (one copy for
 // the whole batch; the per-sample azimuth shift is a rotation folded into w by the host, see
 // gans/models/dusty_v2.py).  Replaces cat(h, PE) + grouped conv (dusty_v2.py:153-161, style.py:105-118).
-extern "C" int dgv2_bmm_nn_cat(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka, int Ks,
-                               int O, const float* bias, int act, float alpha, float scale, int dtype, int ydtype,
-                               void* stream) {
-  return dgv2_bmm_nn_cat_sq(y, xa, xs, w, B, P, Ka, Ks, O, nullptr, bias, act, alpha, scale, dtype, ydtype, nullptr, 0, nullptr,
-                            stream);
-}
-
 extern "C" int dgv2_bmm_nn_cat_sq(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka, int Ks,
                                   int O, const float* row_scale, const float* bias, int act, float alpha, float scale, int dtype, int ydtype,
                                   float* sumsq, int sumsq_cap, int* sumsq_used, void* stream) {
@@ -535,7 +521,7 @@ extern "C" int dgv2_head_bwd(void* y, float* gw, float* gbh, float* gb_up, float
 }
 
 // y [B, P, K] = x [B, P, O] . w [B, K, O]^T (+ resid [B, P, K]), all in `dtype`; 1 <= O <= 4, K a multiple of the
-// 16-byte vector with K / vector dividing 256.  DGV2_ENOTSUP otherwise (use dgv2_bmm_nn).
+// 16-byte vector with K / vector dividing 256.  DGV2_ENOTSUP otherwise (use dgv2_bmm_nn_sq).
 extern "C" int dgv2_bmm_nn_small(void* y, const void* x, const void* w, const void* resid, int B, int P, int O, int K,
                                  int dtype, void* stream) {
   return dgv2_bmm_nn_small_act(y, x, w, resid, B, P, O, K, nullptr, nullptr, 1.f, 1.f, nullptr, nullptr, 0, nullptr, dtype,

@@ -222,11 +222,6 @@ extern "C" int dgv2_mbstd_cat_fwd_x(void* out, float* scratch, const void* x, in
   DGV2_RETURN_LAST();
 }
 
-extern "C" int dgv2_mbstd_cat_fwd(void* out, float* scratch, const void* x, int B, int P, int C, int Cp, int splits,
-                                  int group, int dtype, void* stream) {
-  return dgv2_mbstd_cat_fwd_x(out, scratch, x, B, P, C, Cp, splits, group, dtype, dtype, stream);
-}
-
 // gx [B, P, C] (xdtype, as x) from gout [B, P, Cp] (gdtype: gradient of the concatenated tensor; the padding channels
 // carry none) and x.  gdtype == xdtype, or fp32 gout with bf16 x / gx (the adjoint of the fused cast).
 extern "C" int dgv2_mbstd_cat_bwd_x(void* gx, const void* gout, const void* x, int B, int P, int C, int Cp, int splits,
@@ -248,9 +243,4 @@ extern "C" int dgv2_mbstd_cat_bwd_x(void* gx, const void* gout, const void* x, i
   else
     return DGV2_EINVAL;
   DGV2_RETURN_LAST();
-}
-
-extern "C" int dgv2_mbstd_cat_bwd(void* gx, const void* gout, const void* x, int B, int P, int C, int Cp, int splits,
-                                  int group, int dtype, void* stream) {
-  return dgv2_mbstd_cat_bwd_x(gx, gout, x, B, P, C, Cp, splits, group, dtype, dtype, stream);
 }

@@ -2,7 +2,7 @@
 // kernel the top pyramid levels spend their time in:
 //   y[b,p,o] = act( sum_{k<Ka} xa[b,p,k] w[b,o,k] + sum_{k<Ks} xs[p,k] w[b,o,Ka+k] + bias[o] ) * scale
 // reference: torch.cat([h, pe]) + ModConv2d contraction + FusedLeakyReLU, gans/models/dusty_v2.py:153-162,
-// gans/models/ops/style.py:105-118 (same contract as dgv2_bmm_nn_cat, include/dgv2.h).
+// gans/models/ops/style.py:105-118 (same contract as dgv2_bmm_nn_cat_sq, include/dgv2.h).
 //
 // At level 4 (32768 pixels, Ka = 64, Ks = 512, O = 32) the contraction is 77 GFLOP per 64-sample batch
 // against 0.4 GB of compulsory HBM traffic (xa in, y out) -- provided the 33 MB PE operand is NOT re-read
@@ -473,10 +473,10 @@ __global__ __launch_bounds__(256) void mp_gb_reduce_kernel(float* __restrict__ g
 
 // Data gradient of a PE-free modulated 1x1 layer (conv2 of a generator level: K -> K channels) FUSED with the activation
 // backward of the layer that produced its input (conv1 of the level):
-//   g[b,p,k]    = sum_o gy[b,p,o] wt[b,k,o]                      (rounded to bf16: what dgv2_modconv_pe_fwd stores)
+//   g[b,p,k]    = sum_o gy[b,p,o] wt[b,k,o]                      (rounded to bf16: what dgv2_modconv_pe_fwd_sq stores)
 //   t           = (yref[b,p,k] > 0 ? g : g * alpha) * scale
 //   gpre[b,p,k] = bf16(t * up_scale[k]),     gb[k] = sum_{b,p} bf16(t)
-// -- bit for bit the pair dgv2_modconv_pe_fwd (Ks = 0) + dgv2_bias_act_bwd_rs it replaces (one pass over the gradient
+// -- bit for bit the pair dgv2_modconv_pe_fwd_sq (Ks = 0) + dgv2_bias_act_bwd_rs it replaces (one pass over the gradient
 // instead of three; reference: the autograd chain of ModConv2d -> FusedLeakyReLU, gans/models/ops/style.py:105-118,
 // fused_act.py:46-59).  gy [B,P,K], wt [B,K,K] (conv2's per-sample weights, transposed), yref [B,P,K] bf16; up_scale, gb
 // fp32 [K]; scratch fp32 [scratch_elems] >= *rows_needed * K (call with scratch == NULL to query rows_needed; nothing is
@@ -514,18 +514,11 @@ extern "C" int dgv2_modconv_pe_dgrad_actbwd(void* gpre, float* gb, float* scratc
   DGV2_RETURN_LAST();
 }
 
-// Same contract as dgv2_bmm_nn_cat (bf16 in / bf16 out) for the shapes of the two top generator levels:
+// Same contract as dgv2_bmm_nn_cat_sq (bf16 in / bf16 out) for the shapes of the two top generator levels:
 // (Ka, Ks, O) = (64, 512, 32) (level-4 conv1) and, with Ks = 0 (xs unused), the PE-free shapes
 // (64,0,32), (32,0,64), (128,0,64), (64,0,128), (32,0,32), (64,0,64), (128,0,128), (256,0,256), (256,0,128), (128,0,256) = conv0 /
 // conv2 of levels 4 ... 1 and the data gradients.  Returns DGV2_EINVAL for anything else: callers fall back to
-// dgv2_bmm_nn_cat.
-extern "C" int dgv2_modconv_pe_fwd(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka,
-                                   int Ks, int O, const float* bias, int act, float alpha, float scale, int dtype,
-                                   void* stream) {
-  return dgv2_modconv_pe_fwd_head(y, xa, xs, w, B, P, Ka, Ks, O, nullptr, bias, act, alpha, scale, dtype, nullptr, 0, nullptr,
-                                  nullptr, nullptr, stream);
-}
-
+// dgv2_bmm_nn_cat_sq.
 extern "C" int dgv2_modconv_pe_fwd_sq(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka,
                                       int Ks, int O, const float* row_scale, const float* bias, int act, float alpha,
                                       float scale, int dtype, float* sumsq, int sumsq_cap, int* sumsq_used, void* stream) {

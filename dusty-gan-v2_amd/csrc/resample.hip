@@ -542,8 +542,8 @@ __global__ __launch_bounds__(256) void rs_bias_reduce_kernel(float* __restrict__
 //   y = R(x) * (ref > 0 ? 1 : alpha) * scale,   gb[c] = sum of y over everything but the channel   (fp32 [C])
 // ref: forward output of the activation, [B, out_h, out_w, C] contiguous like y (ldy == C).  scratch: fp32
 // [>= blocks * C] with blocks = *blocks_needed reported when scratch is NULL (query call: nothing is launched).
-// Returns DGV2_ENOTSUP when the streaming kernel does not cover the geometry (callers run dgv2_resample_tab and
-// dgv2_bias_act_bwd).  replaces: Resample adjoint (common.py:105-135) + FusedLeakyReLUFunctionBackward
+// Returns DGV2_ENOTSUP when the streaming kernel does not cover the geometry (callers run dgv2_resample_tab_sq and
+// dgv2_bias_act_bwd_rs).  replaces: Resample adjoint (common.py:105-135) + FusedLeakyReLUFunctionBackward
 // (fused_act.py:22-45) of the discriminator's conv1 -> activation -> blur/down chain (dusty_v2.py:325-345).
 extern "C" int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, int64_t* blocks_needed,
                                         const void* x, const void* ref, const int* idx_h, const float* coef_h,
@@ -571,26 +571,10 @@ extern "C" int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int6
   DGV2_RETURN_LAST();
 }
 
-extern "C" int dgv2_resample_tab(void* y, const void* x, const int* idx_h, const float* coef_h, const int* cnt_h,
-                                 int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew, int B,
-                                 int C, int ldx, int ldy, int in_h, int in_w, int out_h, int out_w, int dtype,
-                                 void* stream) {
-  return dgv2_resample_tab_sq(y, x, idx_h, coef_h, cnt_h, Eh, idx_w, coef_w, cnt_w, Ew, B, C, ldx, ldy, in_h, in_w, out_h,
-                              out_w, dtype, nullptr, 0, nullptr, stream);
-}
-
 // y = resid + resample(x) for packed few-channel images (C in {1, 2, 4}, ld = C): the generator's output pyramid,
 // `o + self.resample(skip)` of SynthesisBlock.forward (dusty_v2.py:179-180), in the resampler's own store -- same bits
 // as the two-launch form (the resampled value is rounded to the storage type before the add).  DGV2_ENOTSUP otherwise.
-extern "C" int dgv2_resample_tab_add(void* y, const void* x, const void* resid, const int* idx_h, const float* coef_h,
-                                     const int* cnt_h, int Eh, const int* idx_w, const float* coef_w, const int* cnt_w,
-                                     int Ew, int B, int C, int in_h, int in_w, int out_h, int out_w, int dtype,
-                                     void* stream) {
-  return dgv2_resample_tab_add_affine(y, x, resid, nullptr, nullptr, idx_h, coef_h, cnt_h, Eh, idx_w, coef_w, cnt_w, Ew, B, C,
-                                      in_h, in_w, out_h, out_w, dtype, stream);
-}
-
-// ... with resid entering as rscale[c] * resid + rbias[c] (fp32 [C] each, both or neither): the level's head output
+// rscale / rbias (fp32 [C] each, both or neither): resid enters as rscale[c] * resid + rbias[c], the level's head output
 // c * (heads' contraction) + bias formed in the same store that adds the up-sampled running image, when the contraction
 // itself came out of conv2's epilogue (dgv2_modconv_pe_fwd_head).
 extern "C" int dgv2_resample_tab_add_affine(void* y, const void* x, const void* resid, const float* rscale,
@@ -614,7 +598,7 @@ extern "C" int dgv2_resample_tab_add_affine(void* y, const void* x, const void* 
   DGV2_RETURN_LAST();
 }
 
-// dgv2_resample_tab with the result stored as e4m3 (OCP fp8, unit scale, saturating at +-448) instead of bf16:
+// dgv2_resample_tab_sq with the result stored as e4m3 (OCP fp8, unit scale, saturating at +-448) instead of bf16:
 // y8 [B,out_h,out_w,C] bytes.  x bf16, C % 8 == 0, Ew <= 4, Eh <= 64 (the streaming kernel); DGV2_ENOTSUP otherwise.
 // The FIR arithmetic is the bf16 kernel's (fp32 accumulation, W pass rounded to bf16 in the ring); only the final
 // store differs.  fp8.hip says which tensors are kept like this.

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void stem_fwd4_kernel(T* __restrict__ y, const
 // The stem's output feeds the first ResidualBlock twice: conv1, and the skip branch through a decimating blur
 // (dusty_v2.py:337-345: self.skip(self.resample(x)), evaluated at the even positions only).  SKIP: the gradient of that
 // blurred / decimated image, gsk [B, Hs, Ws, O], is gathered HERE through the ADJOINT tables of the blur (rows of the
-// full-resolution grid naming the <= E decimated positions they fed, as dgv2_resample_tab takes them) instead of being
+// full-resolution grid naming the <= E decimated positions they fed, as dgv2_resample_tab_sq takes them) instead of being
 // scattered to a full-resolution tensor by a pass of its own, added to conv1's data gradient by another and read back
 // by this one: per iteration 2 x 268 MB of traffic and a launch less at 2B = 128.
 template <typename T>
@@ -361,23 +361,16 @@ extern "C" int dgv2_stem_fwd(void* y, const float* x, const float* w, const floa
   DGV2_RETURN_LAST();
 }
 
-// Number of fp32 scratch elements dgv2_stem_bwd needs: per-block partial sums + the two-channel gxb image.
+// Number of fp32 scratch elements dgv2_stem_bwd_skip needs: per-block partial sums + the two-channel gxb image.
 extern "C" int dgv2_stem_bwd_scratch(int64_t* elems, int B, int H, int W, int O) {
   if (!elems || !stem_ok(B, H, W, O)) return DGV2_EINVAL;
   *elems = (int64_t)STEM_BWD_BLOCKS * 3 * O + (int64_t)B * H * W * 2;
   return 0;
 }
 
-// gw fp32 [O,2], gb fp32 [O], gx fp32 [B,H,W] (NULL: not needed) from gy, y [B,H,W,O] (dtype), x fp32 [B,H,W].
-extern "C" int dgv2_stem_bwd(float* gx, float* gw, float* gb, float* scratch, int64_t scratch_elems, const void* gy,
-                             const void* y, const float* x, const float* w, int B, int H, int W, int O, int ring,
-                             float alpha, float scale, int dtype, void* stream) {
-  return dgv2_stem_bwd_skip(gx, gw, gb, scratch, scratch_elems, gy, y, x, w, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                            nullptr, nullptr, 0, 0, 0, B, H, W, O, ring, alpha, scale, dtype, stream);
-}
-
-// ... with gsk [B, Hs, Ws, O] (dtype; NULL: none), the gradient of a decimating blur of y (the first ResidualBlock's skip
-// branch), gathered through the blur's ADJOINT tables (idx_h / coef_h / cnt_h: H rows of Eh entries naming rows of gsk;
+// gw fp32 [O,2], gb fp32 [O], gx fp32 [B,H,W] (NULL: not needed) from gy, y [B,H,W,O] (dtype), x fp32 [B,H,W],
+// with gsk [B, Hs, Ws, O] (dtype; NULL: none, the tables and Eh / Ew / Hs / Ws are then unused), the gradient of a
+// decimating blur of y (the first ResidualBlock's skip branch), gathered through the blur's ADJOINT tables (idx_h / coef_h / cnt_h: H rows of Eh entries naming rows of gsk;
 // idx_w ...: W rows of Ew entries): the gradient of y is then gy + blur^T(gsk), never materialised.
 extern "C" int dgv2_stem_bwd_skip(float* gx, float* gw, float* gb, float* scratch, int64_t scratch_elems, const void* gy,
                                   const void* y, const float* x, const float* w, const void* gsk, const int* idx_h,

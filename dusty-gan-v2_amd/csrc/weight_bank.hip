@@ -179,17 +179,7 @@ __global__ __launch_bounds__(256) void weight_bank_tiled_kernel(BankArgs a) {
 }  // namespace
 
 // src / wf / wt: HOST arrays of L <= 32 device pointers; O, C, Cpad, kk (= kh*kw), scale: HOST arrays.
-extern "C" int dgv2_conv_weight_bank_ex(void* const* wf, void* const* wt, void* const* w8, void* const* w8t,
-                                        const float* const* src, const int* O, const int* C, const int* Cpad, const int* kk,
-                                        const float* scale, int L, int dtype, void* stream);
-
-extern "C" int dgv2_conv_weight_bank(void* const* wf, void* const* wt, const float* const* src, const int* O,
-                                     const int* C, const int* Cpad, const int* kk, const float* scale, int L,
-                                     int dtype, void* stream) {
-  return dgv2_conv_weight_bank_ex(wf, wt, nullptr, nullptr, src, O, C, Cpad, kk, scale, L, dtype, stream);
-}
-
-// ... with two more, optional outputs per layer: w8[l] != nullptr asks for the staging image of the eight-wave forward
+// Two more, optional outputs per layer: w8[l] != nullptr asks for the staging image of the eight-wave forward
 // conv (conv8.hip, dgv2_conv3x3_fwd8): [O / 64][Cpad / 32][2304 units of 16 bytes in the kernel's slot order], the same
 // values as wf (needs kk == 9, O % 64 == 0, Cpad % 32 == 0, bf16); w8t[l] != nullptr for the image of its stride-1 data
 // gradient (dgv2_conv3x3_dgrad8): [Cpad / 64][O / 32][2304 units], taps in the gradient's order (needs kk == 9,

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE
 
 F32, BF16 = 0, 1
 F16 = 3   # the dgv2_seg_loss_* entries only
-ABI_VERSION = 55
+ABI_VERSION = 56
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -30,11 +30,8 @@ SIGNATURES = {
     "dgv2_abi_version": [],
     "dgv2_fused_bias_act": [_c_ptr] * 4 + [_c_i64] * 3 + [_c_int, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_bias_grad": [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr],
-    "dgv2_bias_act_bwd": [_c_ptr] * 4 + [_c_i64, _c_int, _c_f32, _c_f32, _c_ptr, _c_i64, _c_int, _c_ptr],
     "dgv2_bias_act_bwd_rs": [_c_ptr] * 4 + [_c_i64, _c_int, _c_f32, _c_f32, _c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr],
     "dgv2_surface_normal": [_c_ptr, _c_ptr] + [_c_int] * 5 + [_c_ptr],
-    "dgv2_mbstd_cat_fwd": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr],
-    "dgv2_mbstd_cat_bwd": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr],
     "dgv2_gemm_x3": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_i64, _c_i64,
                      _c_int, _c_f32, _c_ptr],
     "dgv2_pe_wgrad_scratch": [_c_ptr] + [_c_int] * 4,
@@ -44,19 +41,14 @@ SIGNATURES = {
     "dgv2_scale_cast": [_c_ptr] * 3 + [_c_i64, _c_int, _c_int, _c_int, _c_ptr],
     "dgv2_upfirdn2d": [_c_ptr] * 3 + [_c_int] * 15 + [_c_ptr],
     "dgv2_resample": [_c_ptr] * 4 + [_c_int] * 19 + [_c_ptr],
-    "dgv2_resample_tab": [_c_ptr] * 5 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 10 + [_c_ptr],
-    "dgv2_resample_tab_add": [_c_ptr] * 6 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 8 + [_c_ptr],
     "dgv2_resample_tab_add_affine": [_c_ptr] * 8 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 8 + [_c_ptr],
     "dgv2_fourier_feature": [_c_ptr] * 5 + [_c_int] * 8 + [_c_ptr],
     "dgv2_downsample_angle": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr],
-    "dgv2_bmm_nn": [_c_ptr] * 3 + [_c_int] * 6 + [_c_i64, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_int, _c_ptr],
     "dgv2_bmm_tn": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr],
-    "dgv2_bmm_nn_cat": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_int, _c_ptr],
     "dgv2_bmm_nn_cat_sq": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_int, _c_ptr, _c_int, _c_ptr,
                            _c_ptr],
     "dgv2_bmm_nn_sq": [_c_ptr] * 3 + [_c_int] * 6 + [_c_i64, _c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_ptr, _c_int, _c_int, _c_ptr, _c_int,
                        _c_ptr, _c_ptr],
-    "dgv2_modconv_pe_fwd": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_modconv_pe_fwd_sq": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr, _c_int, _c_ptr,
                                _c_ptr],
     "dgv2_modconv_pe_fwd_head": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr, _c_int, _c_ptr,
@@ -133,10 +125,7 @@ SIGNATURES = {
     "dgv2_gemm_stream_tn": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr],
     "dgv2_gemm_stream_tn_cat": [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr],
     "dgv2_bmm_tn_stream_scratch": [_c_ptr] + [_c_int] * 6,
-    "dgv2_bmm_tn_stream": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 6 + [_c_ptr],
-    "dgv2_bmm_tn_stream_x": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 7 + [_c_ptr],
     "dgv2_bmm_tn_stream_ld": [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 7 + [_c_ptr],
-    "dgv2_conv_weight_bank": [_c_ptr] * 8 + [_c_int, _c_int, _c_ptr],
     "dgv2_conv_weight_bank_ex": [_c_ptr] * 10 + [_c_int, _c_int, _c_ptr],
     "dgv2_glin_fwd": [_c_ptr] * 6 + [_c_int] * 3 + [_c_f32, _c_f32, _c_int, _c_f32, _c_int, _c_ptr, _c_ptr],
     "dgv2_glin_dinput": [_c_ptr, _c_int, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_int, _c_f32, _c_f32,
@@ -151,13 +140,11 @@ SIGNATURES = {
     "dgv2_conv3x3_x3_fwd": [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_ptr, _c_ptr],
     "dgv2_conv3x3_fwd8": [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_conv_wgrad_stream_scratch": [_c_ptr] + [_c_int] * 9,
-    "dgv2_conv_wgrad_stream": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 10 + [_c_ptr],
     "dgv2_conv_wgrad_stream_pl": [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_int] * 9 + [_c_f32, _c_int, _c_int, _c_ptr],
     "dgv2_conv_dgrad": [_c_ptr] * 4 + [_c_int] * 11 + [_c_ptr],
     "dgv2_conv_wgrad": [_c_ptr] * 3 + [_c_int] * 11 + [_c_ptr],
     "dgv2_stem_fwd": [_c_ptr] * 4 + [_c_int] * 5 + [_c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_stem_bwd_scratch": [_c_ptr] + [_c_int] * 4,
-    "dgv2_stem_bwd": [_c_ptr] * 4 + [_c_i64] + [_c_ptr] * 4 + [_c_int] * 5 + [_c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_stem_bwd_skip": [_c_ptr] * 4 + [_c_i64] + [_c_ptr] * 8 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 8 + [_c_f32, _c_f32, _c_int,
                                                                                                         _c_ptr],
     "dgv2_gen_tail_fwd": [_c_ptr] * 7 + [_c_int] * 3 + [_c_f32] * 3 + [_c_ptr],

@@ -68,7 +68,7 @@ class _BiasActBackward(Function):
             # per-block column sums folded by a second kernel at every size (the atomics mode without scratch
             # adds in a different order from run to run)
             scratch = torch.empty(2048 * size_b, device=gy.device, dtype=torch.float32)
-            N.call("dgv2_bias_act_bwd", N.ptr(gx), N.ptr(gb), N.ptr(gy), N.ptr(out), rows, size_b, alpha, scale,
+            N.call("dgv2_bias_act_bwd_rs", N.ptr(gx), N.ptr(gb), N.ptr(gy), N.ptr(out), rows, size_b, alpha, scale, None,
                    N.ptr(scratch), scratch.numel(), _dt(gy), N.stream())
         else:
             gx = _bias_act_raw(gy, None, out, 1, alpha, scale, step_b, size_b)
@@ -260,6 +260,11 @@ def _sq_args(dev):
     return torch.empty(_SQ_CAP, device=dev, dtype=torch.float32), _ct.c_int(0)
 
 
+def _sq_tail(sq):
+    """The three sum-of-squares arguments of an entry that has them, from sq = _sq_args(); sq None: no partials."""
+    return (None, 0, None) if sq is None else (N.ptr(sq[0]), _SQ_CAP, _ct.addressof(sq[1]))
+
+
 def _sq_partials(sq, out):
     """The partial sums of squares of out: what the producing kernel left in sq = _sq_args(), or -- sq None, or a kernel
     without that epilogue -- a pass of their own over out."""
@@ -285,13 +290,8 @@ def _resample_raw(x, spec, adjoint, in_hw, out=None, ldy=None, ldx=None, C=None,
         bands = spec.bands(H, W, adjoint, x.device)
         if bands is not None and N.try_call("dgv2_fir_same_mfma", N.ptr(out), N.ptr(x), N.ptr(bands), B, C, oh, ow, N.stream()):
             return out
-    if sq is not None:
-        N.call("dgv2_resample_tab_sq", N.ptr(out), N.ptr(x), N.ptr(ih_idx), N.ptr(ih_coef), N.ptr(ih_cnt), Eh,
-               N.ptr(iw_idx), N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, ldx, ldy, ih, iw, oh, ow, _dt(x), N.ptr(sq[0]),
-               _SQ_CAP, _ct.addressof(sq[1]), N.stream())
-        return out
-    N.call("dgv2_resample_tab", N.ptr(out), N.ptr(x), N.ptr(ih_idx), N.ptr(ih_coef), N.ptr(ih_cnt), Eh,
-           N.ptr(iw_idx), N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, ldx, ldy, ih, iw, oh, ow, _dt(x), N.stream())
+    N.call("dgv2_resample_tab_sq", N.ptr(out), N.ptr(x), N.ptr(ih_idx), N.ptr(ih_coef), N.ptr(ih_cnt), Eh,
+           N.ptr(iw_idx), N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, ldx, ldy, ih, iw, oh, ow, _dt(x), *_sq_tail(sq), N.stream())
     return out
 
 
@@ -346,7 +346,7 @@ def resample(x, spec):
 
 
 class _ResampleAdd(Function):
-    """resid + resample(x) for packed few-channel images in the resampler's store (dgv2_resample_tab_add).
+    """resid + resample(x) for packed few-channel images in the resampler's store (dgv2_resample_tab_add_affine).
     rscale / rbias (fp32 [C], no gradient): resid enters as rscale * resid + rbias -- an affine map that BELONGS to the
     producer of resid (the output heads, whose backward applies it), merely evaluated here: the gradient handed back for
     resid is the gradient of the affine's OUTPUT."""
@@ -413,5 +413,5 @@ def upfirdn2d_raw(x4, kernel, up, down, pad):
 
 
 __all__ = ["input_grads_only", "want_param_grad", "bias_act", "ResampleSpec", "resample_sq", "resample", "resample_add",
-           "sum_squares", "upfirdn2d_raw", "_dt", "_bias_act_raw", "_BiasActBackward", "_SQ_CAP", "_sq_args",
+           "sum_squares", "upfirdn2d_raw", "_dt", "_bias_act_raw", "_BiasActBackward", "_SQ_CAP", "_sq_args", "_sq_tail",
            "_resample_raw"]

@@ -948,11 +948,9 @@ def conv_weight_bank(entries, dtype, image8=None):
     rest = (N.ptr_array(srcs), N.int_array([d[0] for d in dims]), N.int_array([d[1] for d in dims]),
             N.int_array([d[2] for d in dims]), N.int_array([d[3] for d in dims]),
             (_ct.c_float * L)(*[float(s) for _, s, _ in entries]), L, N.dtype_code(flat_f), N.stream())
-    if image8 is None:
-        N.call("dgv2_conv_weight_bank", N.ptr_array(wfs), N.ptr_array(wts), *rest)
-        return list(zip(wfs, wts))
-    N.call("dgv2_conv_weight_bank_ex", N.ptr_array(wfs), N.ptr_array(wts), N.ptr_array(w8s), N.ptr_array(w8ts), *rest)
-    return list(zip(wfs, wts, w8s, w8ts))
+    images = (None, None) if image8 is None else (N.ptr_array(w8s), N.ptr_array(w8ts))
+    N.call("dgv2_conv_weight_bank_ex", N.ptr_array(wfs), N.ptr_array(wts), *images, *rest)
+    return list(zip(wfs, wts)) if image8 is None else list(zip(wfs, wts, w8s, w8ts))
 
 
 _ACTBWD_BLOCKS = {}

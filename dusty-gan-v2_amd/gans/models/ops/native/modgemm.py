@@ -2,7 +2,6 @@
 
 Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
-import ctypes as _ct
 import math
 import os
 
@@ -10,8 +9,7 @@ import torch
 from torch.autograd import Function
 
 import dgv2_native as N
-from . import act_resample
-from .act_resample import _BiasActBackward, _dt
+from .act_resample import _BiasActBackward, _dt, _sq_tail
 
 
 # ---------------------------------------------------------------------------------------
@@ -20,7 +18,7 @@ from .act_resample import _BiasActBackward, _dt
 # ---------------------------------------------------------------------------------------
 _HEAD_FWD = os.environ.get("DGV2_NO_HEAD_FWD") is None   # A/B switch for benchmarking
 _PE_FWD = os.environ.get("DGV2_NO_PE_FWD") is None               # A/B switch for benchmarking
-# (I, O) -> smallest pixel count from which the sample-walking kernel (dgv2_modconv_pe_fwd, PE-free form) takes a
+# (I, O) -> smallest pixel count from which the sample-walking kernel (dgv2_modconv_pe_fwd_sq, PE-free form) takes a
 # per-sample-weight contraction.  Measured at B = 64 (scripts/mb_midgemm.py, profiles/round5_mb_midgemm.txt): it runs these
 # shapes 3.4-3.9x faster than the generic NN engine (whose 128 x 128 tiles re-stage 32-128 KB of per-sample weights per
 # block for four K-steps of work); round 5 added the 128- and 256-channel shapes of levels 2 / 1.
@@ -44,9 +42,12 @@ def _stream_wanted(P, per_sample=True):
     return _GEMM_STREAM and per_sample and P <= _GEMM_STREAM_MAX_P
 
 
-def bmm_nn_sq_call(*args):
-    """dgv2_bmm_nn_sq(*args), on dgv2_gemm_stream_nn where the switch is on and the entry covers the geometry."""
-    if not (_stream_wanted(args[4], args[9] != 0) and N.try_call("dgv2_gemm_stream_nn", *args)):   # P, wstride
+def bmm_nn_sq_call(*args, per_sample=None):
+    """dgv2_bmm_nn_sq(*args), on dgv2_gemm_stream_nn where the switch is on and the entry covers the geometry.
+    per_sample: whether the weights count as per-sample for that routing; None: they do unless the batch shares one
+    (wstride == 0)."""
+    per_sample = args[9] != 0 if per_sample is None else per_sample   # wstride
+    if not (_stream_wanted(args[4], per_sample) and N.try_call("dgv2_gemm_stream_nn", *args)):   # P
         N.call("dgv2_bmm_nn_sq", *args)
 
 
@@ -89,32 +90,21 @@ def _bmm_nn_raw(x3, w3, out_dtype, bias=None, act=0, alpha=0.2, scale=1.0, sq=No
                 and head[0].is_contiguous()):
             hd = torch.empty((B, P, 2), device=x3.device, dtype=torch.float32)
             if N.try_call("dgv2_modconv_pe_fwd_head", N.ptr(y), N.ptr(x3), None, N.ptr(w3), B, P, I, 0, O, N.ptr(row_scale),
-                          N.ptr(bias), act, alpha, scale, _dt(x3), N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0,
-                          _ct.addressof(sq[1]) if sq else None, N.ptr(head[0]), N.ptr(hd), N.stream()):
+                          N.ptr(bias), act, alpha, scale, _dt(x3), *_sq_tail(sq), N.ptr(head[0]), N.ptr(hd), N.stream()):
                 head[1] = hd
                 return y
-        if sq is not None or row_scale is not None:
-            N.call("dgv2_modconv_pe_fwd_sq", N.ptr(y), N.ptr(x3), None, N.ptr(w3), B, P, I, 0, O, N.ptr(row_scale),
-                   N.ptr(bias), act, alpha, scale, _dt(x3), N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0,
-                   _ct.addressof(sq[1]) if sq else None, N.stream())
-            return y
-        N.call("dgv2_modconv_pe_fwd", N.ptr(y), N.ptr(x3), None, N.ptr(w3), B, P, I, 0, O, N.ptr(bias), act, alpha,
-               scale, _dt(x3), N.stream())
+        N.call("dgv2_modconv_pe_fwd_sq", N.ptr(y), N.ptr(x3), None, N.ptr(w3), B, P, I, 0, O, N.ptr(row_scale),
+               N.ptr(bias), act, alpha, scale, _dt(x3), *_sq_tail(sq), N.stream())
         return y
-    if sq is not None or row_scale is not None or resid is not None:
-        if resid is not None:
-            resid = resid.contiguous().to(out_dtype)
-            N.check(resid)
-        bmm_nn_sq_call(N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I,
-                       N.ptr(row_scale), N.ptr(bias), act, alpha, scale, N.ptr(resid), _dt(x3), N.dtype_code(y),
-                       N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None,
-                       N.stream())
-        return y
-    if not (_stream_wanted(P, Bw == B) and N.try_call("dgv2_gemm_stream_nn", N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O,
-                                        0 if Bw == 1 else O * I, None, N.ptr(bias), act, alpha, scale, None, _dt(x3),
-                                        N.dtype_code(y), None, 0, None, N.stream())):
-        N.call("dgv2_bmm_nn", N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I,
-               N.ptr(bias), act, alpha, scale, _dt(x3), N.dtype_code(y), N.stream())
+    # routing onto the stream engine differs at B == Bw == 1 only: a plain call counts the single weight as per-sample,
+    # a call with sq / row_scale / resid as batch-shared (its wstride is 0: the generic engine)
+    plain = sq is None and row_scale is None and resid is None
+    if resid is not None:
+        resid = resid.contiguous().to(out_dtype)
+        N.check(resid)
+    bmm_nn_sq_call(N.ptr(y), N.ptr(x3), N.ptr(w3), B, P, I, O, I, O, 0 if Bw == 1 else O * I, N.ptr(row_scale),
+                   N.ptr(bias), act, alpha, scale, N.ptr(resid), _dt(x3), N.dtype_code(y), *_sq_tail(sq), N.stream(),
+                   per_sample=Bw == B if plain else Bw != 1)
     return y
 
 
@@ -197,7 +187,7 @@ def mod_gemm_act(x, w, bias, alpha=0.2, scale=math.sqrt(2.0)):
 
 
 class _ModGemmCatAct(Function):
-    """Level-input conv with a batch-shared positional encoding (dgv2_bmm_nn_cat / dgv2_bmm_tn_cat):
+    """Level-input conv with a batch-shared positional encoding (dgv2_bmm_nn_cat_sq / dgv2_bmm_tn_cat):
     out = lrelu([xa | xs] @ w^T + b) * scale, xa [B,H,W,Ka] per sample (or None), xs [1,H,W,Ks] shared."""
 
     @staticmethod

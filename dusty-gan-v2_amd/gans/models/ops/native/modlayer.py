@@ -11,7 +11,7 @@ from torch.autograd import Function
 
 import dgv2_native as N
 from . import act_resample, conv, modgemm
-from .act_resample import _BiasActBackward, _bias_act_raw, _dt, _sq_args, _sq_partials
+from .act_resample import _BiasActBackward, _bias_act_raw, _dt, _sq_args, _sq_partials, _sq_tail
 from .conv import _bmm_tn_small
 from .modgemm import _bmm_nn_raw, bmm_nn_cat_sq_call, bmm_tn_call, bmm_tn_cat_call
 
@@ -26,9 +26,9 @@ _TN_SCRATCH = {}
 
 
 def _bmm_tn_stream(g3, xa, B, H, W_, I, O, shared=False, out=None):
-    """gw fp32 [B,O,I] = per-sample sum over pixels of gy [B,H*W,O] x xa [B,H,W,I] (dgv2_bmm_tn_stream); shared: xa is
+    """gw fp32 [B,O,I] = per-sample sum over pixels of gy [B,H*W,O] x xa [B,H,W,I] (dgv2_bmm_tn_stream_ld); shared: xa is
     one image [1,H,W,I] contracted against every sample (the positional encoding).  out: a [B,O,ld] fp32 tensor
-    (ld >= I) whose first I columns receive the result in place (dgv2_bmm_tn_stream_ld)."""
+    (ld >= I) whose first I columns receive the result in place."""
     key = (B, H, W_, I, O)
     if key not in _TN_SCRATCH:
         n = _ct.c_int64(0)
@@ -48,7 +48,7 @@ def _pe_cat_fwd(out, xa, xs, wb, cvec, bias32, act, cfg, sq):
     B, H, W_, Otot = out.shape
     Ka = 0 if xa is None else xa.shape[3]
     Ks = xs.shape[3]
-    tail = (N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0, _ct.addressof(sq[1]) if sq else None, N.stream())
+    tail = (*_sq_tail(sq), N.stream())
     if modgemm._PE_FWD and out.dtype == torch.bfloat16 and (Ka, Ks, Otot) in ((64, 512, 32), (128, 512, 64), (256, 512, 128)):
         # top pyramid levels: pixel-tile blocks walking the samples, PE fragments in registers
         N.call("dgv2_modconv_pe_fwd_sq", N.ptr(out), N.ptr(xa), N.ptr(xs), N.ptr(wb), B, H * W_, Ka, Ks, Otot, N.ptr(cvec),
@@ -546,7 +546,7 @@ _DGRAD_ACT_ROWS = {}
 def _dgrad_actbwd(g3, wt, xa, up):
     """Data gradient of a PE-free K -> K modulated layer (conv2 of a generator level) fused with the activation backward
     of the layer that produced its input xa (conv1 of the level): dgv2_modconv_pe_dgrad_actbwd, bit for bit the pair
-    dgv2_modconv_pe_fwd + dgv2_bias_act_bwd_rs.  up = dict(link, alpha, scale, cvec) as for _head_dgrad_actbwd; the
+    dgv2_modconv_pe_fwd_sq + dgv2_bias_act_bwd_rs.  up = dict(link, alpha, scale, cvec) as for _head_dgrad_actbwd; the
     upstream layer's backward finds link["done"] and the bias gradient in link["gb"].  None where it does not apply."""
     B, P, O = g3.shape
     K = wt.shape[1]

@@ -2,7 +2,6 @@
 
 Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
-import ctypes as _ct
 import math
 import os
 
@@ -11,7 +10,7 @@ from torch.autograd import Function
 
 import dgv2_native as N
 from . import act_resample, conv
-from .act_resample import _dt, _resample_raw, _sq_args, _sq_partials
+from .act_resample import _dt, _resample_raw, _sq_args, _sq_partials, _sq_tail
 from .modgemm import _bmm_nn_raw, bmm_tn_call
 from .modlayer import _bmm_tn_stream, _mod_act_bwd, _mod_wgrad, pe_wgrad
 
@@ -102,7 +101,7 @@ def up2_lag_sumsq(x, spec):
     sq = _sq_args(x.device)
     N.check(x)
     if not N.try_call("dgv2_up2_lag_sumsq", N.ptr(x), N.ptr(gram[0]), N.ptr(gram[1]), N.ptr(gram[2]), N.ptr(gram[3]), B,
-                      H, W, C, _dt(x), N.ptr(sq[0]), act_resample._SQ_CAP, _ct.addressof(sq[1]), N.stream()):
+                      H, W, C, _dt(x), *_sq_tail(sq), N.stream()):
         return None
     return sq[0][:sq[1].value]
 
@@ -156,8 +155,7 @@ def resample_sq_only(x, spec):
     C = x.shape[3]
     N.check(x)
     N.call("dgv2_resample_tab_sq", None, N.ptr(x), N.ptr(ih_idx), N.ptr(ih_coef), N.ptr(ih_cnt), Eh, N.ptr(iw_idx),
-           N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, C, C, H, W, Ho, Wo, _dt(x), N.ptr(sq[0]), act_resample._SQ_CAP,
-           _ct.addressof(sq[1]), N.stream())
+           N.ptr(iw_coef), N.ptr(iw_cnt), Ew, B, C, C, C, H, W, Ho, Wo, _dt(x), *_sq_tail(sq), N.stream())
     return sq[0][:sq[1].value]
 
 
@@ -194,8 +192,7 @@ def mod_up_prepare(h, xs, wb, spec, act=True, alpha=0.2, scale=math.sqrt(2.0), w
     N.check(h, wb)
     if not N.try_call("dgv2_modconv_up_t_lag", N.ptr(t), N.ptr(wimg), N.ptr(h), N.ptr(wb), gain,
                       *(N.ptr(g) for g in (gram if gram is not None else (None,) * 4)), B, hl, wl, Ka, Ks, Otot, I, Ka,
-                      _dt(h), N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0,
-                      _ct.addressof(sq[1]) if sq else None, N.stream()):
+                      _dt(h), *_sq_tail(sq), N.stream()):
         return None
     return t, wimg, (sq[0][:sq[1].value] if sq else None)
 
@@ -232,8 +229,7 @@ class _ModUpPrepared(Function):
         N.check(t, xsf, wimg, bias32, cvec)
         N.call("dgv2_modconv_up_fwd", N.ptr(out), N.ptr(t), N.ptr(xsf), N.ptr(wimg), B, H, W_, hl, wl, Ks, Otot,
                N.ptr(ih), N.ptr(ch), N.ptr(iw), N.ptr(cw), N.ptr(bias32), N.ptr(in_scale), act, cfg["alpha"],
-               cfg["scale"], _dt(h), N.ptr(sq[0]) if sq else None, act_resample._SQ_CAP if sq else 0,
-               _ct.addressof(sq[1]) if sq else None, N.stream())
+               cfg["scale"], _dt(h), *_sq_tail(sq), N.stream())
         ctx.cfg = dict(cfg, has_bias=bias is not None)
         ctx.save_for_backward(h, xs, wb, out if cfg["act"] else None, cvec, wt)
         if cfg["want_sq"]:

@@ -3,7 +3,7 @@ under differentiation (every backward is built from Functions of the family), so
 itself be differentiated on the HIP kernels -- the path-length regulariser (reference: gans/trainer.py:308-365) asks for
 d/dtheta of |d(image . noise)/dw|.
 
-    y  = [xa | xs] . w^T     cat_gemm(xa, xs, w)      dgv2_bmm_nn / dgv2_bmm_nn_cat
+    y  = [xa | xs] . w^T     cat_gemm(xa, xs, w)      dgv2_bmm_nn_sq / dgv2_bmm_nn_cat_sq
     gw = gy^T [xa | xs]      cat_gemm_tn(gy, xa, xs)  dgv2_bmm_tn / dgv2_bmm_tn_cat
 
 xa [B,P,Ka] per-sample activations (or None), xs [1,P,Ks] the batch-shared positional encoding (constant: no gradient,
@@ -27,8 +27,8 @@ def _cat_nn(xa, xs, wc, out_dtype):
     Ka = 0 if xa is None else xa.shape[2]
     y = torch.empty((B, P, O), device=xs.device, dtype=out_dtype)
     N.check(xa, xs, wc)
-    N.call("dgv2_bmm_nn_cat", N.ptr(y), N.ptr(xa), N.ptr(xs), N.ptr(wc), B, P, Ka, Ks, O, None, 0, 0.2, 1.0, _dt(xs),
-           N.dtype_code(y), N.stream())
+    N.call("dgv2_bmm_nn_cat_sq", N.ptr(y), N.ptr(xa), N.ptr(xs), N.ptr(wc), B, P, Ka, Ks, O, None, None, 0, 0.2, 1.0, _dt(xs),
+           N.dtype_code(y), None, 0, None, N.stream())
     return y
 
 

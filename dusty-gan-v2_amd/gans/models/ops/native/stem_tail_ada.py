@@ -60,17 +60,15 @@ class _Stem(Function):
         gw = torch.empty((O, 2), device=gy.device, dtype=torch.float32)
         gb = torch.empty(O, device=gy.device, dtype=torch.float32)
         gx = torch.empty((B, H * W_), device=gy.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        tabs, Hs, Ws = (None, None, None, 0, None, None, None, 0), 0, 0   # no skip gradient: the stem's backward alone
         if gsk is not None:
             gsk = gsk.contiguous().to(y.dtype)
             Hs, Ws = down.out_size(H, W_)
             (ih, chh, nh, Eh), (iw, cw, nw, Ew) = down.tables(H, W_, True, gy.device)   # the blur's adjoint tables
+            tabs = (N.ptr(ih), N.ptr(chh), N.ptr(nh), Eh, N.ptr(iw), N.ptr(cw), N.ptr(nw), Ew)
             N.check(gsk)
-            N.call("dgv2_stem_bwd_skip", N.ptr(gx), N.ptr(gw), N.ptr(gb), N.ptr(scratch), scratch.numel(), N.ptr(gy), N.ptr(y),
-                   N.ptr(x3), N.ptr(w32), N.ptr(gsk), N.ptr(ih), N.ptr(chh), N.ptr(nh), Eh, N.ptr(iw), N.ptr(cw), N.ptr(nw), Ew,
-                   Hs, Ws, B, H, W_, O, int(ring), alpha, scale, _dt(y), N.stream())
-        else:
-            N.call("dgv2_stem_bwd", N.ptr(gx), N.ptr(gw), N.ptr(gb), N.ptr(scratch), scratch.numel(), N.ptr(gy), N.ptr(y),
-                   N.ptr(x3), N.ptr(w32), B, H, W_, O, int(ring), alpha, scale, _dt(y), N.stream())
+        N.call("dgv2_stem_bwd_skip", N.ptr(gx), N.ptr(gw), N.ptr(gb), N.ptr(scratch), scratch.numel(), N.ptr(gy), N.ptr(y),
+               N.ptr(x3), N.ptr(w32), N.ptr(gsk), *tabs, Hs, Ws, B, H, W_, O, int(ring), alpha, scale, _dt(y), N.stream())
         return (None if gx is None else gx.reshape(xshape)), gw.reshape(wshape), gb, None, None, None, None, None
 
 

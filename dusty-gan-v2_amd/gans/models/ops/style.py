@@ -3,7 +3,7 @@
 Parameter / buffer names and shapes match the reference (`weight` [1,O,I,k,k], `mod.module.*`,
 `bias` [1,O,1,1], `ema_var` []).  The per-sample weights are prepared with small fp32 tensor ops
 (autograd carries the chain into `weight` and the style Linear); the contraction -- the grouped
-conv of style.py:105-118 -- is the MFMA batched GEMM dgv2_bmm_nn / dgv2_bmm_tn."""
+conv of style.py:105-118 -- is the MFMA batched GEMM dgv2_bmm_nn_sq / dgv2_bmm_tn."""
 import numpy as np
 import torch
 import torch.nn as nn

@@ -69,10 +69,7 @@ int dgv2_bias_grad(float* gb, const void* x, int64_t size_x, int64_t step_b, int
  * Returns DGV2_EINVAL for shapes it does not cover (C % vec != 0 or (C/vec) not dividing 256);
  * callers then use dgv2_fused_bias_act(grad=1) + dgv2_bias_grad. */
 /* scratch (optional fp32 [>= 2048*C]): many-block mode with a partial-sum reduce instead of atomics. */
-int dgv2_bias_act_bwd(void* gx, float* gb, const void* gy, const void* ref, int64_t rows, int C,
-                      float alpha, float scale, float* scratch, int64_t scratch_elems, int dtype,
-                      void* stream);
-/* ... with an optional per-channel factor row_scale fp32 [C] on the STORED gradient only (gb sums the unscaled
+/* row_scale (fp32 [C], NULL = none): an optional per-channel factor on the STORED gradient only (gb sums the unscaled
  * one): backward of y = act(acc * row_scale[c] + b[c]) with respect to acc. */
 int dgv2_bias_act_bwd_rs(void* gx, float* gb, const void* gy, const void* ref, int64_t rows, int C,
                          float alpha, float scale, const float* row_scale, float* scratch,
@@ -116,40 +113,33 @@ int dgv2_resample(void* y, const void* x, const float* taps_h, const float* taps
 /* Table-driven form of the same operator (the hot-path entry): per axis the sparse rows of the
  * resampling matrix, built once on the host per (spec, size, direction): idx/coef [n_out, E]
  * row-major, cnt [n_out] valid entries per row.  y[b,ho,wo,:] = sum_a sum_c coef_h[ho,a] *
- * coef_w[wo,c] * x[b, idx_h[ho,a], idx_w[wo,c], :].  Same reference lines as dgv2_resample. */
-int dgv2_resample_tab(void* y, const void* x, const int* idx_h, const float* coef_h, const int* cnt_h,
-                      int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew,
-                      int B, int C, int ldx, int ldy, int in_h, int in_w, int out_h, int out_w,
-                      int dtype, void* stream);
-
-/* y = resid + dgv2_resample_tab(x) for packed few-channel images (C in {1, 2, 4}, ld = C; y, x, resid of `dtype`):
- * `o + self.resample(skip)` of SynthesisBlock.forward (dusty_v2.py:179-180) in one launch, bit-equal to the two-launch
- * form.  DGV2_ENOTSUP for other channel counts / misaligned pointers. */
-int dgv2_resample_tab_add(void* y, const void* x, const void* resid, const int* idx_h, const float* coef_h,
-                          const int* cnt_h, int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew,
-                          int B, int C, int in_h, int in_w, int out_h, int out_w, int dtype, void* stream);
-/* ... with resid entering as rscale[c] * resid + rbias[c] (fp32 [C], both or neither): `c * heads(x) + bias` of Head.forward
- * (dusty_v2.py:30-57) formed in the same store when the heads' contraction left conv2's epilogue (dgv2_modconv_pe_fwd_head). */
-int dgv2_resample_tab_add_affine(void* y, const void* x, const void* resid, const float* rscale, const float* rbias,
-                                 const int* idx_h, const float* coef_h, const int* cnt_h, int Eh, const int* idx_w,
-                                 const float* coef_w, const int* cnt_w, int Ew, int B, int C, int in_h, int in_w, int out_h,
-                                 int out_w, int dtype, void* stream);
-
-/* dgv2_resample_tab that can also leave the sum of squares of what it wrote (the next modulated conv's input
- * statistic, ModConv2d.forward style.py:98-103: x.square().mean() for the EMA) as per-block partials, saving a
- * separate pass over the activation: sumsq fp32 [sumsq_cap] device buffer (NULL = plain dgv2_resample_tab);
- * *sumsq_used (host) = number of partials written, 0 when this launch configuration cannot provide them
- * (the caller then runs dgv2_sum_squares).  Partials feed dgv2_ema_scalar(sumsq, nsum = *sumsq_used). */
+ * coef_w[wo,c] * x[b, idx_h[ho,a], idx_w[wo,c], :].  Same reference lines as dgv2_resample.
+ * It can also leave the sum of squares of what it wrote (the next modulated conv's input statistic, ModConv2d.forward
+ * style.py:98-103: x.square().mean() for the EMA) as per-block partials, saving a separate pass over the activation:
+ * sumsq fp32 [sumsq_cap] device buffer (NULL with sumsq_cap = 0 and sumsq_used = NULL: the plain resampler, nothing
+ * else is written); *sumsq_used (host) = number of partials written, 0 when this launch configuration cannot provide
+ * them (the caller then runs dgv2_sum_squares).  Partials feed dgv2_ema_scalar(sumsq, nsum = *sumsq_used). */
 int dgv2_resample_tab_sq(void* y, const void* x, const int* idx_h, const float* coef_h, const int* cnt_h,
                          int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew,
                          int B, int C, int ldx, int ldy, int in_h, int in_w, int out_h, int out_w,
                          int dtype, float* sumsq, int sumsq_cap, int* sumsq_used, void* stream);
 
+/* y = resid + dgv2_resample_tab_sq(x) for packed few-channel images (C in {1, 2, 4}, ld = C; y, x, resid of `dtype`):
+ * `o + self.resample(skip)` of SynthesisBlock.forward (dusty_v2.py:179-180) in one launch, bit-equal to the two-launch
+ * form.  DGV2_ENOTSUP for other channel counts / misaligned pointers.
+ * rscale / rbias (fp32 [C], both or neither; NULL = resid enters as it is): resid enters as rscale[c] * resid + rbias[c],
+ * `c * heads(x) + bias` of Head.forward (dusty_v2.py:30-57) formed in the same store when the heads' contraction left
+ * conv2's epilogue (dgv2_modconv_pe_fwd_head). */
+int dgv2_resample_tab_add_affine(void* y, const void* x, const void* resid, const float* rscale, const float* rbias,
+                                 const int* idx_h, const float* coef_h, const int* cnt_h, int Eh, const int* idx_w,
+                                 const float* coef_w, const int* cnt_w, int Ew, int B, int C, int in_h, int in_w, int out_h,
+                                 int out_w, int dtype, void* stream);
+
 /* Resampling (normally the ADJOINT tables of a blur/down) followed by the backward of a fused bias + leaky-ReLU in the
  * same pass:  y = R(x) * (ref > 0 ? 1 : alpha) * scale,  gb[c] = sum of the stored y over everything but the channel.
  * ref = forward OUTPUT of the activation, [B, out_h, out_w, C] contiguous like y; gb fp32 [C].
  * scratch fp32 [>= *blocks_needed * C]; a call with scratch == NULL only reports *blocks_needed.  DGV2_ENOTSUP when
- * the streaming kernel does not cover the geometry (then: dgv2_resample_tab + dgv2_bias_act_bwd).
+ * the streaming kernel does not cover the geometry (then: dgv2_resample_tab_sq + dgv2_bias_act_bwd_rs).
  * replaces: Resample adjoint (common.py:105-135) + FusedLeakyReLUFunctionBackward (fused_act.py:22-45) of the
  * discriminator's conv1 -> activation -> blur/down chain (dusty_v2.py:325-345) run backwards. */
 int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, int64_t* blocks_needed,
@@ -161,13 +151,13 @@ int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch
 /* Same-size separable FIR (the blur in front of the discriminator's stride-2 convs, and its adjoint) on the MFMA cores,
  * bf16, x / y [B,H,W,C] contiguous:  y = R x.  Each pass is one 16x16x32 MFMA per 16 outputs x 16 channels with the
  * filter band as a constant operand (fir_mfma.hip).
- * dgv2_fir_same_mfma_prep builds the band operands ONCE from sparse-row tables exactly as dgv2_resample_tab takes them
+ * dgv2_fir_same_mfma_prep builds the band operands ONCE from sparse-row tables exactly as dgv2_resample_tab_sq takes them
  *   (bands: device buffer of >= *bytes_needed bytes, 16-byte aligned; bands == NULL only reports *bytes_needed).
  *   Contract on the tables (a violation raises DGV2_STATUS_FIR_TABLE in *status and the bands are unusable):
  *   |idx_h[ho][a] - ho| <= 4,  (idx_w[wo][e] - wo + 8) mod W < 24,  every coefficient -- and every sum of the
  *   coefficients of one row that name the same input -- exactly representable in bf16.  DGV2_ENOTSUP unless
  *   H % 8 == 0 and W % 32 == 0.
- * dgv2_fir_same_mfma / _actbwd: DGV2_ENOTSUP unless C % 32 == 0, H % 8 == 0, W % 32 == 0 (then: dgv2_resample_tab /
+ * dgv2_fir_same_mfma / _actbwd: DGV2_ENOTSUP unless C % 32 == 0, H % 8 == 0, W % 32 == 0 (then: dgv2_resample_tab_sq /
  *   dgv2_resample_tab_actbwd, whose contracts they share: same scratch protocol for the bias gradient).
  * replaces: Blur / Resample(up = down = 1) (gans/models/ops/common.py:105-135) at gans/models/dusty_v2.py:325-345, its
  *   adjoint, and FusedLeakyReLUFunctionBackward (gans/models/ops/fused_act/fused_act.py:22-45) behind it. */
@@ -210,10 +200,9 @@ int dgv2_downsample_angle(float* out, const float* in, const float* shift, const
  * Fused epilogue (nn only): y = act(y + bias[o]) with bias fp32 [O] or NULL, act 0 = none /
  * 3 = leaky-ReLU(alpha) * scale -- the FusedLeakyReLU that follows each trunk conv
  * (fused_bias_act_kernel.cu:19-65), saving one pass over the activation.
+ * The nn entry (dgv2_bmm_nn_sq, declared with its concatenating sibling below) has three more optional operands:
+ * row_scale, resid and the sum-of-squares partials; NULL / 0 in those positions is the contraction as written here.
  * ------------------------------------------------------------------------- */
-int dgv2_bmm_nn(void* y, const void* x, const void* w, int B, int P, int I, int O,
-                int ldx, int ldy, int64_t wstride, const float* bias, int act, float alpha, float scale,
-                int dtype, int ydtype, void* stream);
 int dgv2_bmm_tn(float* gw, const void* gy, const void* x, int B, int P, int I, int O,
                 int ldgy, int ldx, int dtype, void* stream);
 
@@ -224,10 +213,8 @@ int dgv2_bmm_tn(float* gw, const void* gy, const void* x, int B, int P, int I, i
  * is a per-frequency rotation folded into w by the host); w [B,O,Ka+Ks].  Ka, Ks multiples of the
  * 16-byte vector.  replaces: torch.cat([h, pe]) + ModConv2d contraction + FusedLeakyReLU,
  *   gans/models/dusty_v2.py:153-162, gans/models/ops/style.py:105-118.
- * tn: gw[b,o,:] = sum_p gy[b,p,o] * [xa[b,p,:] | xs[p,:]]  (fp32 [B,O,Ka+Ks]). */
-int dgv2_bmm_nn_cat(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka, int Ks,
-                    int O, const float* bias, int act, float alpha, float scale, int dtype, int ydtype,
-                    void* stream);
+ * tn: gw[b,o,:] = sum_p gy[b,p,o] * [xa[b,p,:] | xs[p,:]]  (fp32 [B,O,Ka+Ks]).
+ * The entries are dgv2_bmm_nn_cat_sq and dgv2_bmm_tn_cat, declared below. */
 /* The same level-input conv with the block's up-sampling COMMUTED past the contraction (a 1x1 conv acts per pixel, the
  * FIR per channel): W_a . up2(h) == up2(W_a . h), so the xa columns run at a quarter of the pixels (T = W_a . h at the
  * previous level's resolution, dgv2_modconv_up_t below) and this entry evaluates
@@ -284,10 +271,12 @@ int dgv2_modconv_up_t_lag(void* tcm, void* wimg, const void* h, const void* w, f
  *   (x = Resample(up=2)(h), gans/models/dusty_v2.py:153-155), without a pass at the up-sampled size. */
 int dgv2_up2_lag_sumsq(const void* h, const float* ghd, const float* gho, const float* gwd, const float* gwo, int B,
                        int Hin, int Win, int C, int dtype, float* sumsq, int sumsq_cap, int* sumsq_used, void* stream);
-/* dgv2_bmm_nn / dgv2_bmm_nn_cat that also leave per-block partial sums of squares of the stored outputs
- * (contract as in dgv2_resample_tab_sq), with an optional per-output-channel factor ahead of the bias:
- * y = act(acc * row_scale[o] + bias[o]) (row_scale fp32 [O] or NULL) -- the input-magnitude factor of
- * ModConv2d (style.py:98-103) when the weights were prepared by dgv2_mod_prep_all_fwd. */
+/* The nn contraction and the level-input conv above (x / w / ldx / ldy / wstride / ydtype, xa / xs, bias / act / alpha /
+ * scale as described there).  Both can also leave per-block partial sums of squares of the stored outputs (sumsq /
+ * sumsq_cap / sumsq_used: contract as in dgv2_resample_tab_sq; NULL, 0, NULL = none), and take an optional
+ * per-output-channel factor ahead of the bias: y = act(acc * row_scale[o] + bias[o]) (row_scale fp32 [O], NULL = 1) --
+ * the input-magnitude factor of ModConv2d (style.py:98-103) when the weights were prepared by dgv2_mod_prep_all_fwd.
+ * resid (dgv2_bmm_nn_sq only): NULL = nothing is added. */
 int dgv2_bmm_nn_sq(void* y, const void* x, const void* w, int B, int P, int I, int O, int ldx, int ldy,
                    int64_t wstride, const float* row_scale, const float* bias, int act, float alpha, float scale,
                    const void* resid /* optional [B,P,ldy] in ydtype, added to the result */, int dtype, int ydtype,
@@ -327,14 +316,13 @@ int dgv2_head_bwd(void* y, float* gw, float* gbh, float* gb_up, float* scratch, 
                   const void* ref, const float* row_scale, float alpha, float ascale, int B, int P, int O, int K, int dtype,
                   void* stream);
 
-/* The same contraction as dgv2_bmm_nn_cat, organised for the two top pyramid levels where it dominates
+/* The same contraction as dgv2_bmm_nn_cat_sq, organised for the two top pyramid levels where it dominates
  * the generator ((Ka, Ks, O) = (64, 512, 32) and, as two 32-channel slabs, (128, 512, 64); bf16): a block owns a tile of pixels and walks the
  * samples, the shared PE fragments stay in registers, xa streams straight into registers and only the
  * per-sample weights go through LDS (LDS-DMA, double-buffered) -- HBM sees xa and y once, the PE once per block.
- * Returns DGV2_EINVAL for any other shape / dtype (use dgv2_bmm_nn_cat). */
-int dgv2_modconv_pe_fwd(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka, int Ks,
-                        int O, const float* bias, int act, float alpha, float scale, int dtype, void* stream);
-/* ... with the per-block sum-of-squares partials of the stored outputs (contract as in dgv2_resample_tab_sq). */
+ * Returns DGV2_EINVAL for any other shape / dtype (use dgv2_bmm_nn_cat_sq).
+ * row_scale (fp32 [O], NULL = 1) as there; sumsq / sumsq_cap / sumsq_used: the per-block sum-of-squares partials of the
+ * stored outputs (contract as in dgv2_resample_tab_sq; NULL, 0, NULL = none). */
 int dgv2_modconv_pe_fwd_sq(void* y, const void* xa, const void* xs, const void* w, int B, int P, int Ka, int Ks,
                            int O, const float* row_scale, const float* bias, int act, float alpha, float scale, int dtype, float* sumsq,
                            int sumsq_cap, int* sumsq_used, void* stream);
@@ -356,7 +344,7 @@ int dgv2_modconv_pe_fwd_head(void* y, const void* xa, const void* xs, const void
  *   g[b,p,k]    = sum_o gy[b,p,o] wt[b,k,o]                    (rounded to bf16)
  *   t           = (yref[b,p,k] > 0 ? g : g * alpha) * scale
  *   gpre[b,p,k] = bf16(t * up_scale[k]),   gb[k] = sum_{b,p} bf16(t)
- * -- bit for bit what dgv2_modconv_pe_fwd (Ks = 0) followed by dgv2_bias_act_bwd_rs produce.
+ * -- bit for bit what dgv2_modconv_pe_fwd_sq (Ks = 0) followed by dgv2_bias_act_bwd_rs produce.
  * gy [B,P,K], wt [B,K,K], yref [B,P,K] (the upstream layer's forward output), gpre [B,P,K]: bf16; up_scale, gb fp32 [K];
  * scratch fp32 [scratch_elems] >= *rows_needed * K.  scratch == NULL: only *rows_needed is written, nothing is launched.
  * K in {32, 64} (generator levels 4 / 3), dtype DGV2_BF16; DGV2_ENOTSUP otherwise. */
@@ -456,11 +444,14 @@ int dgv2_sum_squares(float* acc, const void* x, int64_t N, int C, int ld, int dt
  *   conv engine, Cp > C, both multiples of the 16-byte vector).  B = splits * group * m: `splits` independent
  *   sub-batches (real | fake in one pass), group members strided by m as in the reference.  scratch: fp32
  *   [>= 64 * B / group].  bwd: gx [B, P, C] from the gradient of `out` and x.
+ * The epilogue's cast is folded in: x / gx in xdtype, out (ydtype) / gout (gdtype) the same (the plain form: pass xdtype
+ * twice) or fp32 for a bf16 x -- x.float() of the reference's fp32 epilogue (gans/models/dusty_v2.py:394-395) and its
+ * adjoint without their own passes over the activation.
  * ------------------------------------------------------------------------- */
-int dgv2_mbstd_cat_fwd(void* out, float* scratch, const void* x, int B, int P, int C, int Cp, int splits,
-                       int group, int dtype, void* stream);
-int dgv2_mbstd_cat_bwd(void* gx, const void* gout, const void* x, int B, int P, int C, int Cp, int splits,
-                       int group, int dtype, void* stream);
+int dgv2_mbstd_cat_fwd_x(void* out, float* scratch, const void* x, int B, int P, int C, int Cp, int splits, int group,
+                         int xdtype, int ydtype, void* stream);
+int dgv2_mbstd_cat_bwd_x(void* gx, const void* gout, const void* x, int B, int P, int C, int Cp, int splits, int group,
+                         int xdtype, int gdtype, void* stream);
 /* C[i, j] = scale * sum_{t < T} A(i, t) B(j, t) in fp32-equivalent arithmetic on the bf16 matrix cores: every operand
  * value is split into three bf16 planes (x = h + m + l, residual <= 2^-26 |x|) while its tile is staged into LDS and a
  * product is taken as six bf16 products with fp32 accumulation (the dropped terms are below 2^-25 of the product).
@@ -483,13 +474,6 @@ int dgv2_gemm_x3(float* c, float* scratch, int64_t scratch_elems, const float* a
 int dgv2_pe_wgrad_scratch(int64_t* elems, int B, int P, int O, int Ks);
 int dgv2_pe_wgrad(float* gw, float* scratch, int64_t scratch_elems, const void* g, const void* pe, int B, int P, int O,
                   int Ks, int64_t ldo, int col0, void* stream);
-/* The same with the epilogue's cast folded in: x / gx in xdtype, out (ydtype) / gout (gdtype) the same or fp32 for a
- * bf16 x -- x.float() of the reference's fp32 epilogue (gans/models/dusty_v2.py:394-395) and its adjoint without their
- * own passes over the activation. */
-int dgv2_mbstd_cat_fwd_x(void* out, float* scratch, const void* x, int B, int P, int C, int Cp, int splits, int group,
-                         int xdtype, int ydtype, void* stream);
-int dgv2_mbstd_cat_bwd_x(void* gx, const void* gout, const void* x, int B, int P, int C, int Cp, int splits, int group,
-                         int xdtype, int gdtype, void* stream);
 
 /* ---------------------------------------------------------------------------
  * dense convolution with ring padding (discriminator)
@@ -498,7 +482,7 @@ int dgv2_mbstd_cat_bwd_x(void* gx, const void* gout, const void* x, int B, int P
  * x [B,H,W,C]; w [O,kh,kw,C] (channels-last filter); y [B,Ho,Wo,O];
  * pad on every side, Ho = (H + 2*pad - kh)/stride + 1.
  *   fwd  : y  = conv(pad(x), w), optionally followed by the fused bias + leaky-ReLU epilogue
- *          (bias fp32 [O] or NULL, act 0 / 3, alpha, scale) as in dgv2_bmm_nn
+ *          (bias fp32 [O] or NULL, act 0 / 3, alpha, scale) as in dgv2_bmm_nn_sq
  *   dgrad: gx = pad^T(conv^T(gy, w))         (gx [B,H,W,C]; wt = w transposed to [C,kh,kw,O];
  *          gxp_scratch [B,H+2pad,W+2pad,C] holds the padded-domain gradient, NULL if pad == 0)
  *   wgrad: gw[o,ky,kx,c] = sum gy * pad(x)   (fp32 [O,kh,kw,C], overwritten)
@@ -521,26 +505,20 @@ int dgv2_conv_wgrad_direct(float* gw, const void* gy, const void* x, int B, int 
 
 /* Per-sample 1x1 weight gradient of the modulated conv (ModConv2d autograd, style.py:105-118) on the streaming
  * engine above: gw fp32 [B,O,C] = sum over the H*W pixels of sample b of gy [B,H,W,O] x [B,H,W,C]; splits stay
- * inside an image.  C, O multiples of the 16-byte vector and O*C a multiple of 4. */
-int dgv2_bmm_tn_stream_scratch(int64_t* elems, int B, int H, int W, int C, int O, int dtype);
-int dgv2_bmm_tn_stream(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
-                       int B, int H, int W, int C, int O, int dtype, void* stream);
-/* ... with x_shared != 0: x is ONE image [H, W, C] contracted against every sample's gy -- the weight gradient of the
- * batch-shared positional-encoding columns, gw[b,o,c] = sum_p gy[b,p,o] * pe[p,c]. */
-int dgv2_bmm_tn_stream_x(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
-                         int x_shared, int B, int H, int W, int C, int O, int dtype, void* stream);
-/* ... with a row pitch: gw is [B, O, ldo] (ldo >= C, ldo % 4 == 0; 0 = contiguous), the columns [0, C) of the layer's
+ * inside an image.  C, O multiples of the 16-byte vector and O*C a multiple of 4.
+ * x_shared != 0 (0 = x holds one image per sample): x is ONE image [H, W, C] contracted against every sample's gy -- the
+ * weight gradient of the batch-shared positional-encoding columns, gw[b,o,c] = sum_p gy[b,p,o] * pe[p,c] (DESIGN.md
+ * section 5.3).
+ * ldo, a row pitch: gw is [B, O, ldo] (ldo >= C, ldo % 4 == 0; 0 = contiguous [B, O, C]), the columns [0, C) of the layer's
  * whole [B, O, Ka + Ks] weight gradient written in place next to the PE columns of dgv2_pe_wgrad -- no concatenation. */
+int dgv2_bmm_tn_stream_scratch(int64_t* elems, int B, int H, int W, int C, int O, int dtype);
 int dgv2_bmm_tn_stream_ld(float* gw, int64_t ldo, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
                           int x_shared, int B, int H, int W, int C, int O, int dtype, void* stream);
 
 /* Compute-dtype copies of all conv weights of the discriminator in ONE launch (L <= 32): from each fp32
  * master [O,C,kh,kw] (EqualLR runtime scale folded in: common.py:158-184) the forward layout
- * wf [O, kh*kw, Cpad] and the data-gradient layout wt [Cpad, kh*kw, O].  HOST arrays of device pointers. */
-int dgv2_conv_weight_bank(void* const* wf, void* const* wt, const float* const* src, const int* O,
-                          const int* C, const int* Cpad, const int* kk, const float* scale, int L,
-                          int dtype, void* stream);
-/* ... with two more, optional outputs per layer (array or entry NULL: none).  w8t[l]: the staging image of the stride-1
+ * wf [O, kh*kw, Cpad] and the data-gradient layout wt [Cpad, kh*kw, O].  HOST arrays of device pointers.
+ * w8 / w8t: two more, optional outputs per layer (array or entry NULL: none).  w8t[l]: the staging image of the stride-1
  * data gradient dgv2_conv3x3_dgrad8 -- [Cpad / 64][O / 32][2304 units], row = t' * 64 + c % 64 with the gradient's tap
  * order t' = 8 - (ky * 3 + kx), plane = (o % 32) / 8 (needs Cpad % 64 == 0, O % 32 == 0).  w8[l]: the STAGING IMAGE of
  * the eight-wave forward conv dgv2_conv3x3_fwd8 -- [O / 64][Cpad / 32][2304 units of 16 bytes], unit (row = tap * 64 + o % 64,
@@ -572,7 +550,7 @@ int dgv2_conv3x3_fwd8(void* y, const void* x, const void* w8, int B, int Hin, in
 int dgv2_conv3x3_dgrad8(void* gx, const void* gy, const void* w8t, int B, int H, int W, int C, int O, const void* resid,
                         int dtype, void* stream);
 /* The STRIDE-2 data gradient of the 3x3 ring conv (pad 1) on the eight-wave engine (conv8_s2d.hip), from the transposed row
- * weights wt [C, 9, O] (dgv2_conv_weight_bank's wt): gx [B, 2 Hg, 2 Wg, C] (bf16) from gy [B, Hg, Wg, O], the replicate row of
+ * weights wt [C, 9, O] (dgv2_conv_weight_bank_ex's wt): gx [B, 2 Hg, 2 Wg, C] (bf16) from gy [B, Hg, Wg, O], the replicate row of
  * output row 0 included -- two launches, one per output row parity (three or six taps, two column classes each) on eight-row
  * tiles where those fill the chip, one four-class launch on four-row tiles otherwise.
  * replaces: the cuDNN data gradient autograd calls for ops.Conv2d (common.py:187-210) at ResidualBlock.conv2
@@ -627,15 +605,12 @@ int dgv2_conv_x3_images(void* w3, void* w3t, const void* w, int O, int Cp, void*
  * slice of the batch's pixel tiles; the per-slice partial sums go to `scratch` (plain stores) and are
  * reduced into gw fp32 [O, k*k, C] (overwritten).  k in {1,3}, pad = (k-1)/2, stride in {1,2}, C and O
  * multiples of the 16-byte vector.  dgv2_conv_wgrad_stream_scratch reports the fp32 element count the
- * scratch buffer must hold for a geometry. */
+ * scratch buffer must hold for a geometry.
+ * The entry writes scale * gw (1.f: the plain gradient), and with param_layout != 0 in the parameter's own layout
+ * [O, C, k, k] (nn.Conv2d weight, common.py:187-210) instead of [O, k*k, C] (0): the EqualLR factor and the layout
+ * change of the weight gradient cost no separate pass. */
 int dgv2_conv_wgrad_stream_scratch(int64_t* elems, int B, int H, int W, int C, int O, int k, int stride,
                                    int pad, int dtype);
-int dgv2_conv_wgrad_stream(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
-                           int B, int H, int W, int C, int O, int k, int stride, int pad, int ring,
-                           int dtype, void* stream);
-/* ... writing scale * gw, and with param_layout != 0 in the parameter's own layout [O, C, k, k] (nn.Conv2d weight,
- * common.py:187-210) instead of [O, k*k, C]: the EqualLR factor and the layout change of the weight gradient cost
- * no separate pass. */
 int dgv2_conv_wgrad_stream_pl(float* gw, float* scratch, int64_t scratch_elems, const void* gy, const void* x,
                               int B, int H, int W, int C, int O, int k, int stride, int pad, int ring,
                               float scale, int param_layout, int dtype, void* stream);
@@ -687,7 +662,7 @@ int dgv2_conv_taps_ld(void* y, int ldy, const void* x, const void* w, int B, int
  * residual added to the rounded product: bit for bit what dgv2_conv_taps computes for the same operands):
  *   dgv2_conv1x1_fwd:    y [B,P,O]  = x [B,P,C]  . wf [O,C]^T (+ resid [B,P,O])
  *   dgv2_conv1x1_dgrad:  gx [B,P,C] = gy [B,P,O] . wt [C,O]^T (+ resid [B,P,C])
- * wf / wt: the weight bank's forward / transposed layouts (dgv2_conv_weight_bank; any runtime scale already folded in);
+ * wf / wt: the weight bank's forward / transposed layouts (dgv2_conv_weight_bank_ex; any runtime scale already folded in);
  * no bias, no activation.  DGV2_BF16, C % 32 == 0, O % 32 == 0, contraction length (C forward, O data gradient) <= 512,
  * 16-byte aligned pointers; DGV2_ENOTSUP otherwise: callers then run dgv2_conv_taps on the same operands.
  * replaces: ops.Conv2d forward / data gradient (gans/models/ops/common.py:187-210) of ResidualBlock.skip behind its
@@ -736,15 +711,13 @@ int dgv2_gemm_stream_tn_cat(float* gw, const void* gy, const void* xa, const voi
 int dgv2_stem_fwd(void* y, const float* x, const float* w, const float* bias, int B, int H, int W, int O,
                   int ring, float alpha, float scale, int ydtype, void* stream);
 int dgv2_stem_bwd_scratch(int64_t* elems, int B, int H, int W, int O);
-int dgv2_stem_bwd(float* gx, float* gw, float* gb, float* scratch, int64_t scratch_elems, const void* gy,
-                  const void* y, const float* x, const float* w, int B, int H, int W, int O, int ring,
-                  float alpha, float scale, int dtype, void* stream);
-/* ... with the gradient of the first ResidualBlock's skip branch folded in: gsk [B,Hs,Ws,O] (dtype) = dL/d(blur_down(y)),
+/* The backward, optionally with the gradient of the first ResidualBlock's skip branch folded in: gsk [B,Hs,Ws,O]
+ * (dtype) = dL/d(blur_down(y)),
  * the decimating blur in front of ResidualBlock.skip (gans/models/dusty_v2.py:337-345), gathered through the blur's ADJOINT
  * tables (idx_h / coef_h / cnt_h: H rows of Eh entries naming rows of gsk; idx_w / coef_w / cnt_w: W rows of Ew entries,
- * exactly the tables dgv2_resample_tab takes for the adjoint pass): dL/dy = gy + blur_down^T(gsk) is never materialised
+ * exactly the tables dgv2_resample_tab_sq takes for the adjoint pass): dL/dy = gy + blur_down^T(gsk) is never materialised
  * (it was scattered to a [B,H,W,O] tensor by one pass, added to conv1's data gradient by another and read back here).
- * gsk NULL: dgv2_stem_bwd. */
+ * gsk NULL: the stem's backward alone (dL/dy = gy); the six tables may then be NULL and Eh = Ew = Hs = Ws = 0. */
 int dgv2_stem_bwd_skip(float* gx, float* gw, float* gb, float* scratch, int64_t scratch_elems, const void* gy, const void* y,
                        const float* x, const float* w, const void* gsk, const int* idx_h, const float* coef_h,
                        const int* cnt_h, int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew, int Hs,
@@ -974,7 +947,7 @@ int dgv2_emd_matchcost_grad(float* grad1, float* grad2, const float* match, cons
 /* y8 [B,H,W,C] (e4m3 bytes) = R x for a same-size separable resampling: dgv2_fir_same_mfma with the result rounded to
  * e4m3 (saturating at +-448) at the store.  replaces: Resample(up = down = 1) / Blur, gans/models/ops/common.py:105-135. */
 int dgv2_fir_same_mfma_q8(void* y8, const void* x, const void* bands, int B, int C, int H, int W, void* stream);
-/* dgv2_resample_tab (x bf16, tables as there) with the result stored as e4m3 bytes y8 [B,out_h,out_w,C]; C % 8 == 0,
+/* dgv2_resample_tab_sq (x bf16, tables as there) with the result stored as e4m3 bytes y8 [B,out_h,out_w,C]; C % 8 == 0,
  * Ew <= 4, Eh <= 64, else DGV2_ENOTSUP.  replaces: Resample, gans/models/ops/common.py:105-135. */
 int dgv2_resample_tab_q8(void* y8, const void* x, const int* idx_h, const float* coef_h, const int* cnt_h, int Eh,
                          const int* idx_w, const float* coef_w, const int* cnt_w, int Ew, int B, int C, int in_h,
@@ -986,7 +959,7 @@ int dgv2_resample_tab_q8(void* y8, const void* x, const int* idx_h, const float*
 int dgv2_fp8_quant_weights(void* const* w8, const void* const* src, const int* O, const int* C, const int* kk,
                            const float* eq, int n, float* descale, void* amax, void* stream);
 /* y (bf16) = x (e4m3) * scale for n elements, n % 16 == 0: the saved e4m3 activations as the bf16 operand of the
- * weight-gradient stream (dgv2_conv_wgrad_stream). */
+ * weight-gradient stream (dgv2_conv_wgrad_stream_pl). */
 int dgv2_fp8_dequant(void* y, const void* x, int64_t n, float scale, void* stream);
 /* dgv2_conv_taps (single class, no extras, overwrite) on e4m3 operands x8 [B,Hin,Win,Cin], w8 [O,wtaps,Cin]:
  *   y (bf16) = act( acc * acc_scale[0] + resid + bias ) * scale,  acc_scale a DEVICE scalar (dgv2_fp8_quant_weights).

@@ -1,4 +1,4 @@
-"""conv2's data gradient of a generator level + conv1's activation backward: the two launches (dgv2_modconv_pe_fwd with
+"""conv2's data gradient of a generator level + conv1's activation backward: the two launches (dgv2_modconv_pe_fwd_sq with
 Ks = 0, dgv2_bias_act_bwd_rs) against the fused dgv2_modconv_pe_dgrad_actbwd; us per launch at B = 64."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 """Generator level-4 conv1 (B x 64x512, Ka = 64 from 32x256, Ks = 512, O = 32, bf16): the path that materialises up2(h)
-(resample_sq + dgv2_modconv_pe_fwd) against the commuted one (low-res dgv2_bmm_nn + dgv2_modconv_up_fwd + statistic-only
+(resample_sq + dgv2_modconv_pe_fwd_sq) against the commuted one (low-res dgv2_bmm_nn_sq + dgv2_modconv_up_fwd + statistic-only
 pass); us per launch."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

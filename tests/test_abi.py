@@ -10,6 +10,10 @@ import pytest
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "dgv2.h")
+# forwarding entries retired at ABI 56: each only re-called a wider entry with neutral arguments
+RETIRED = ("dgv2_bias_act_bwd", "dgv2_bmm_nn", "dgv2_bmm_nn_cat", "dgv2_modconv_pe_fwd", "dgv2_resample_tab",
+           "dgv2_resample_tab_add", "dgv2_mbstd_cat_fwd", "dgv2_mbstd_cat_bwd", "dgv2_bmm_tn_stream", "dgv2_bmm_tn_stream_x",
+           "dgv2_conv_wgrad_stream", "dgv2_stem_bwd", "dgv2_conv_weight_bank")
 
 
 def parse_header():
@@ -44,6 +48,9 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(N.LIB_PATH)
     for name in protos:
         assert hasattr(lib, name), f"{name} declared in dgv2.h but not exported"
+    for name in RETIRED:
+        assert not hasattr(lib, name), f"{name} is retired but still exported"
+        assert name not in N.SIGNATURES and name not in protos, f"{name} is retired but still declared"
     assert N.lib.dgv2_abi_version() == N.ABI_VERSION
 
 

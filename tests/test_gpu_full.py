@@ -1,6 +1,6 @@
 """Full-size parity on the GPU (64x512, channel widths 512..32): the HIP modules in fp32 parity mode against the
 fixture the REFERENCE produced at that size (tests/golden/model_full.npz: G step, D step, lazy R1, eval forwards of
-BASELINE configs[0] / [1]).  These shapes take kernels the reduced configuration never reaches (dgv2_modconv_pe_fwd and
+BASELINE configs[0] / [1]).  These shapes take kernels the reduced configuration never reaches (dgv2_modconv_pe_fwd_sq and
 its slabs, streaming weight gradients, weight bank, fused stem, one-launch data gradients).  Tolerance: 1e-3 relative
 (north_star).  Then the bf16 throughput mode against the same fixture with a stated bf16 tolerance."""
 import pytest
@@ -163,7 +163,7 @@ def test_fp32_d_step_and_r1_match_reference(g_full, angle, truth):
 
 def test_fp32_discriminator_at_batch_4_matches_reference():
     """The HIP discriminator (fp32 parity mode) on tests/golden/model_full_b4.npz: full width, B = 4, so the minibatch
-    standard deviation runs with its configured group of 4 (dgv2_mbstd_cat_fwd/_bwd): logits, loss and every parameter
+    standard deviation runs with its configured group of 4 (dgv2_mbstd_cat_fwd_x/_bwd_x): logits, loss and every parameter
     gradient (norm and leading slice) within 1e-3 of the reference's CPU run."""
     from conftest import load_golden
     from helpers import build_models, full_cfg

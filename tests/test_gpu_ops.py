@@ -202,7 +202,7 @@ def test_bmm_bf16_random_tolerance(nat):
                                           (128, 0, 64, 300, 2), (64, 0, 128, 260, 2), (32, 0, 32, 300, 2), (64, 0, 64, 300, 2),
                                           (128, 0, 128, 300, 3), (256, 0, 256, 200, 3), (256, 0, 128, 140, 2), (128, 0, 256, 260, 2)])
 def test_modconv_pe_fwd_matches_reference(nat, Ka, Ks, O, P, B):
-    """dgv2_modconv_pe_fwd (pixel-tile blocks walking the samples, shared PE in registers) against the
+    """dgv2_modconv_pe_fwd_sq (pixel-tile blocks walking the samples, shared PE in registers) against the
     einsum of the reference's cat([h, pe]) + per-sample 1x1 conv + bias + lrelu (dusty_v2.py:153-162,
     style.py:105-118): exact on integer operands, bf16 tolerance on random ones; ragged pixel tile."""
     import dgv2_native as N
@@ -220,9 +220,8 @@ def test_modconv_pe_fwd_matches_reference(nat, Ka, Ks, O, P, B):
         bd = bias.to(DEV)
         for act in (0, 3):
             y = torch.full((B, P, O), float("nan"), device=DEV, dtype=torch.bfloat16)
-            N.call("dgv2_modconv_pe_fwd", N.ptr(y), N.ptr(xad), N.ptr(xsd) if Ks else None, N.ptr(wd), B, P, Ka, Ks, O,
-                   N.ptr(bd), act,
-                   0.2, math.sqrt(2.0), N.BF16, N.stream())
+            N.call("dgv2_modconv_pe_fwd_sq", N.ptr(y), N.ptr(xad), N.ptr(xsd) if Ks else None, N.ptr(wd), B, P, Ka, Ks, O,
+                   None, N.ptr(bd), act, 0.2, math.sqrt(2.0), N.BF16, None, 0, None, N.stream())
             xcat = torch.cat([xad.double().cpu(), xsd.double().cpu()[None].expand(B, P, Ks)], dim=2)
             want = torch.einsum("bpi,boi->bpo", xcat, wd.double().cpu()) + bias.double()
             if act == 3:
@@ -265,7 +264,7 @@ def test_modconv_pe_sumsq_partials_are_reproducible(nat, P, I, O):
 
 @pytest.mark.parametrize("C,dtype", [(2, torch.float32), (1, torch.float32), (4, torch.bfloat16), (2, torch.bfloat16)])
 def test_resample_add_is_the_two_launch_form(nat, C, dtype):
-    """dgv2_resample_tab_add: `o + self.resample(skip)` of the generator's output pyramid (dusty_v2.py:179-180) in the
+    """dgv2_resample_tab_add_affine: `o + self.resample(skip)` of the generator's output pyramid (dusty_v2.py:179-180) in the
     resampler's store -- bit-equal to resample followed by the add, gradients included."""
     g = torch.Generator().manual_seed(3)
     spec = nat.ResampleSpec([1, 3, 3, 1], up=(2, 2))
@@ -458,7 +457,7 @@ def test_heads_layer_takes_one_weight_gradient_engine_through_both_nodes(nat, mo
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-5), (torch.bfloat16, 8e-3)])
 @pytest.mark.parametrize("B,splits,group", [(8, 1, 4), (16, 2, 4), (6, 2, 4), (4, 1, 4)])
 def test_mbstd_cat_matches_composed_reference(nat, dtype, tol, B, splits, group):
-    """dgv2_mbstd_cat_fwd/_bwd against MinibatchStdDev (group members strided through the batch, biased variance,
+    """dgv2_mbstd_cat_fwd_x/_bwd_x against MinibatchStdDev (group members strided through the batch, biased variance,
     eps 1e-8, mean over H, W, C) + concat + zero channel padding composed from torch ops (common.py:226-250);
     `splits` sub-batches are independent, a sub-batch smaller than the group shrinks the group."""
     g = torch.Generator().manual_seed(17)
@@ -640,7 +639,7 @@ def test_linear_f32_double_backward_matches_float64(nat):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_adjoint_resample_fused_with_activation_backward(nat, dtype):
     """dgv2_resample_tab_actbwd (adjoint blur/down + bias/leaky-ReLU backward + bias gradient in one pass) against the
-    two kernels it replaces (dgv2_resample_tab adjoint, then dgv2_bias_act_bwd): same stored gradient bit for bit,
+    two kernels it replaces (dgv2_resample_tab_sq adjoint, then dgv2_bias_act_bwd_rs): same stored gradient bit for bit,
     bias gradient to summation-order tolerance.  Odd batch, several strips and column blocks."""
     g = torch.Generator().manual_seed(23)
     B, H, W, C = 3, 16, 64, 32
@@ -776,7 +775,7 @@ def test_producers_leave_sum_of_squares_partials(nat, g_ops):
         head = (N.ptr(xa), N.ptr(xs) if Ks else None, N.ptr(w), B, P, Ka, Ks, O)
         tail = (N.ptr(bias), 3, 0.2, math.sqrt(2.0), N.BF16)
         args = (*head, None, *tail)   # row_scale = NULL
-        N.call("dgv2_modconv_pe_fwd", N.ptr(y0), *head, *tail, N.stream())
+        N.call("dgv2_modconv_pe_fwd_sq", N.ptr(y0), *args, None, 0, None, N.stream())
         N.call("dgv2_modconv_pe_fwd_sq", N.ptr(y1), *args, N.ptr(buf), 8192, ctypes.addressof(used), N.stream())
         assert torch.equal(y0, y1) and used.value > 0
         want = y1.double().square().sum().item()
@@ -798,11 +797,13 @@ def test_producers_leave_sum_of_squares_partials(nat, g_ops):
         used = ctypes.c_int(-1)
         tail = (N.ptr(bias), 3, 0.2, math.sqrt(2.0), N.BF16, N.BF16)
         if Ks:
-            N.call("dgv2_bmm_nn_cat", N.ptr(y0), N.ptr(xa), N.ptr(xs), N.ptr(w), B, P, Ka, Ks, O, *tail, N.stream())
+            N.call("dgv2_bmm_nn_cat_sq", N.ptr(y0), N.ptr(xa), N.ptr(xs), N.ptr(w), B, P, Ka, Ks, O, None, *tail, None, 0, None,
+                   N.stream())
             N.call("dgv2_bmm_nn_cat_sq", N.ptr(y1), N.ptr(xa), N.ptr(xs), N.ptr(w), B, P, Ka, Ks, O, None, *tail, N.ptr(buf),
                    8192, ctypes.addressof(used), N.stream())
         else:
-            N.call("dgv2_bmm_nn", N.ptr(y0), N.ptr(xa), N.ptr(w), B, P, Ka, O, Ka, O, O * Ka, *tail, N.stream())
+            N.call("dgv2_bmm_nn_sq", N.ptr(y0), N.ptr(xa), N.ptr(w), B, P, Ka, O, Ka, O, O * Ka, None, *tail[:4], None, *tail[4:],
+                   None, 0, None, N.stream())
             N.call("dgv2_bmm_nn_sq", N.ptr(y1), N.ptr(xa), N.ptr(w), B, P, Ka, O, Ka, O, O * Ka, None, *tail[:4], None, *tail[4:],
                    N.ptr(buf), 8192, ctypes.addressof(used), N.stream())
             # residual operand: added after the activation, the statistic covers what was stored
@@ -843,7 +844,7 @@ def test_stem_matches_composed_reference(nat, ring, dtype, W):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_bias_act_backward_many_block_mode(nat, dtype):
-    """The >= 65536-row path of dgv2_bias_act_bwd (2048 blocks, partial column sums + reduce kernel) against the
+    """The >= 65536-row path of dgv2_bias_act_bwd_rs (2048 blocks, partial column sums + reduce kernel) against the
     fused_leaky_relu backward of the reference (fused_act.py:36-60): gx = g * (y > 0 ? 1 : 0.2) * sqrt2, gb = sum gx."""
     g = torch.Generator().manual_seed(3)
     B, H, W, C = 2, 64, 520, 32   # 66560 rows, not a multiple of the block tiling
@@ -950,7 +951,7 @@ def test_grouped_linear_style_affines_and_mapping_network(nat, B, shared, monkey
 
 @pytest.mark.parametrize("B,H,W,I,O", [(3, 32, 64, 64, 32), (2, 20, 96, 128, 64), (2, 8, 40, 32, 32)])
 def test_bmm_tn_stream_per_sample_weight_gradient(nat, B, H, W, I, O):
-    """dgv2_bmm_tn_stream (streaming split-K engine, every split inside one image) = the per-sample weight
+    """dgv2_bmm_tn_stream_ld (streaming split-K engine, every split inside one image) = the per-sample weight
     gradient of the modulated 1x1 conv, gw[b,o,c] = sum_p gy[b,p,o] x[b,p,c] (ModConv2d autograd, style.py:105-118):
     exact on integer-valued bf16 operands, ragged tiles included."""
     import ctypes
@@ -964,14 +965,14 @@ def test_bmm_tn_stream_per_sample_weight_gradient(nat, B, H, W, I, O):
     N.call("dgv2_bmm_tn_stream_scratch", ctypes.addressof(n), B, H, W, I, O, N.BF16)
     scratch = torch.empty(n.value, device=DEV)
     gw = torch.full((B, O, I), float("nan"), device=DEV)
-    N.call("dgv2_bmm_tn_stream", N.ptr(gw), N.ptr(scratch), scratch.numel(), N.ptr(gd), N.ptr(xd), B, H, W, I, O, N.BF16,
-           N.stream())
+    N.call("dgv2_bmm_tn_stream_ld", N.ptr(gw), 0, N.ptr(scratch), scratch.numel(), N.ptr(gd), N.ptr(xd), 0, B, H, W, I, O,
+           N.BF16, N.stream())
     want = torch.einsum("bhwo,bhwc->boc", gy, x)
     assert torch.equal(gw.cpu(), want)
 
 
 def test_bmm_tn_stream_shared_operand(nat):
-    """dgv2_bmm_tn_stream_x with x_shared: one image contracted against every sample's gradient
+    """dgv2_bmm_tn_stream_ld with x_shared: one image contracted against every sample's gradient
     (gw[b,o,c] = sum_p gy[b,p,o] pe[p,c], the positional-encoding columns of the modulated convs)."""
     g = torch.Generator().manual_seed(12)
     B, H, W, I, O = 3, 16, 64, 64, 32
@@ -1659,7 +1660,7 @@ def test_modconv_up_commuted_upsampling_matches_cat_path(nat, Ka, O):
     """dgv2_modconv_up_fwd (conv1 of a generator level with the up-sampling commuted past the 1x1 contraction,
     csrc/modconv_up.hip) + its backward against (a) the float64 statement of the reference, act(c * ([up2(h) | PE] . W) +
     bias) (dusty_v2.py:153-162, style.py:105-118, Resample common.py:105-135), and (b) the existing path that
-    materialises up2(h) (resample + dgv2_modconv_pe_fwd), outputs and every gradient; plus the statistic-only pass."""
+    materialises up2(h) (resample + dgv2_modconv_pe_fwd_sq), outputs and every gradient; plus the statistic-only pass."""
     from gans.models.ops.common import Resample
     g = torch.Generator().manual_seed(77)
     B, hl, wl, F = 3, 8, 32, 256
@@ -2148,7 +2149,7 @@ def test_d_tail_matches_the_composed_ops_in_float64(B, K):
 @pytest.mark.parametrize("B,P,K", [(3, 4096, 32), (2, 4096 + 200, 64), (5, 2048, 128), (7, 8192, 64), (64, 32768, 32)])
 def test_dgrad_with_upstream_activation_backward_is_bit_identical_to_the_two_launches(nat, B, P, K):
     """dgv2_modconv_pe_dgrad_actbwd (conv2's data gradient of a generator level with conv1's activation backward in its
-    epilogue) against the two launches it replaces -- dgv2_modconv_pe_fwd (the same sample-walking kernel, Ks = 0) and
+    epilogue) against the two launches it replaces -- dgv2_modconv_pe_fwd_sq (the same sample-walking kernel, Ks = 0) and
     dgv2_bias_act_bwd_rs: the stored accumulator gradient BIT for bit (the epilogue masks / scales the bf16-rounded
     gradient exactly as the separate pass reads it), the bias gradient to summation order.  Partial pixel tiles, odd
     batches (the prefetch of the next sample's upstream outputs wraps at the last one), both channel counts; the last
