@@ -29,7 +29,7 @@ extern "C" {
 #define DGV2_F32 0
 #define DGV2_BF16 1
 #define DGV2_FP8 2 /* OCP e4m3fn bytes; only where an entry says so (the *_fp8 / *_q8 entries) */
-#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits) */
+#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits; dgv2_fire_fwd) */
 #define DGV2_EINVAL (-1)
 #define DGV2_ENOTSUP (-3) /* valid request that this build's kernels do not cover: use the documented fallback */
 
@@ -1176,6 +1176,40 @@ int dgv2_seg_loss_forward(float* loss_map, int64_t* pred, int64_t* conf, float* 
 int dgv2_seg_loss_backward(void* g_logit, const void* logit, const int64_t* label, const float* mask,
                            const float* alpha, const float* gout, const float* sums, int B, int C, int H, int W,
                            float gamma, int dtype, int per_pixel, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Fire module of the SqueezeSeg trunks, evaluation mode (fire.hip; semseg/models/squeezeseg_v1.py / _v2.py here)
+ * replaces: Fire.forward, semseg/models/squeezeseg_v2.py:39-56 and squeezeseg_v1.py:8-24, over the ConvReLU /
+ *   ConvReLUNorm / DeconvReLU sequences of semseg/models/common.py:56-111 (conv, ReLU, eval batch norm, transposed conv,
+ *   cat), and the decoder's residual adds of squeezeseg_v2.py:169-172 -- 10 to 13 launches -- with ONE launch.
+ * x [B,Cin,H,W], skip (or NULL) and y [B,E1+E3,H,Wout] are contiguous NCHW of one `dtype` (DGV2_F32, DGV2_BF16 or
+ * DGV2_F16); Wout = 2 W with `up`, else W.  Every parameter is float32 in the layout of its torch module:
+ * w_s [Cs,Cin,1,1], w_d [Cs(in),Cs(out),1,4] (ConvTranspose2d), w_1 [E1,Cs,1,1], w_3 [E3,Cs,3,3], biases per channel.
+ *   s  = N_s(relu(W_s x + b_s))
+ *   u  = relu(sum_{ci,k} s[ci][h][w] w_d[ci][co][0][k] + b_d[co])  over the taps (w, k) with w' = 2 w - 1 + k and
+ *        0 <= w < W (others dropped)                      only with `up`; else u = s
+ *   e1 = N_1(relu(W_1 u + b_1))
+ *   e3 = N_3(relu(W_3 * u + b_3))         3x3, zero padding 1 APPLIED TO u: a position outside the image contributes 0,
+ *                                         not N_s(relu(b_s)) and not the squeeze of a clamped or wrapped pixel
+ *   y  = cat(e1, e3) [+ skip]
+ * N(v) = (v - mean) * (gamma * (1 / sqrtf(var + eps))) + beta per channel, in float32, folded in the kernel from the
+ * four vectors (correctly rounded divide and square root); the four pointers of a set all NULL: no batch norm (V1's
+ * ConvReLU).  Accumulation is float32 throughout.  DGV2_F32 runs the exact f32-input MFMA (one k-ordered fmaf chain per
+ * output); the 16-bit dtypes convert the weights to that dtype in registers, hold s and u in it (one rounding each)
+ * and run the 16x16x32 MFMA.  No tensor with Cs channels reaches memory; no atomics, no scratch buffer; the output
+ * bits do not depend on the grid.
+ * Range: Cin, Cs, E1, E3 multiples of 16, 16 <= Cin <= 512, 16 <= Cs <= 64, 16 <= E1, E3 <= 256; B, H, W >= 1.
+ * DGV2_EINVAL, nothing launched and y untouched: outside that range, another dtype, a null required pointer (y, x,
+ * the four conv weights and biases; w_d / b_d exactly when up == 1), a conv weight that is not 16-byte aligned (they
+ * are read with 16-byte loads), a batch-norm set that is partly null, a negative or NaN eps, up not 0 / 1, more than
+ * 2^31 - 1 blocks.
+ * ------------------------------------------------------------------------- */
+int dgv2_fire_fwd(void* y, const void* x, const void* skip, const float* w_s, const float* b_s, const float* g_s,
+                  const float* beta_s, const float* mean_s, const float* var_s, const float* w_d, const float* b_d,
+                  const float* w_1, const float* b_1, const float* g_1, const float* beta_1, const float* mean_1,
+                  const float* var_1, const float* w_3, const float* b_3, const float* g_3, const float* beta_3,
+                  const float* mean_3, const float* var_3, float eps_s, float eps_1, float eps_3, int B, int Cin,
+                  int Cs, int E1, int E3, int H, int W, int up, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
