@@ -345,24 +345,37 @@ bool fm_covers(int B, int C, int H, int W) {
 
 constexpr size_t FM_LDS = (size_t)FM_XBYTES + FM_ZBYTES + FM_YBYTES;
 
-int64_t fm_band_bytes(int H, int W) { return 1024 * ((int64_t)H / FM_RS + 1 + W / 16); }
+// BYTES of the band buffer of one same-size table set (0: the MFMA kernel does not take the map)
+int64_t fm_band_bytes(int H, int W) {
+  if (H < FM_RS || H % FM_RS || W < FM_CT || W % FM_CT) return 0;
+  return 1024 * ((int64_t)H / FM_RS + 1 + W / 16);
+}
+
+// fp32 workspace of dgv2_fir_same_mfma_actbwd: one row of C partial bias sums per (sample, column tile); 0: not covered
+int64_t fm_actbwd_elems(int B, int C, int H, int W) { return fm_covers(B, C, H, W) ? (int64_t)B * (W / FM_CT) * C : 0; }
 
 }  // namespace
 
+// (BYTES, not fp32 elements: the band buffer is not a float workspace)
+extern "C" int dgv2_fir_same_mfma_prep_scratch(int64_t* bytes, int H, int W) {
+  if (!bytes) return DGV2_EINVAL;
+  *bytes = fm_band_bytes(H, W);
+  return *bytes ? 0 : DGV2_ENOTSUP;
+}
+
 // Band operands of dgv2_fir_same_mfma for one SAME-SIZE table set (sparse rows exactly as for dgv2_resample_tab_sq): built
-// once, kept by the caller next to the tables.  bands: device buffer of >= *bytes_needed bytes (a call with bands == NULL
-// only reports *bytes_needed).  Contract on the tables (a violation raises bit DGV2_STATUS_FIR_TABLE of the caller's device word *status):
+// once, kept by the caller next to the tables.  bands: device buffer of >= dgv2_fir_same_mfma_prep_scratch BYTES.
+// Contract on the tables (a violation raises bit DGV2_STATUS_FIR_TABLE of the caller's device word *status):
 //   |idx_h[ho][a] - ho| <= 4,   (idx_w[wo][e] - wo + 8) mod W < 24,   every coefficient -- and every sum of the
 //   coefficients of one row that name the same input -- exact in bf16.
 // DGV2_ENOTSUP unless H % 8 == 0 and W % 32 == 0.
-extern "C" int dgv2_fir_same_mfma_prep(void* bands, int64_t bands_bytes, int64_t* bytes_needed, const int* idx_h,
-                                       const float* coef_h, const int* cnt_h, int Eh, const int* idx_w, const float* coef_w,
-                                       const int* cnt_w, int Ew, int H, int W, int* status, void* stream) {
-  if (H < FM_RS || H % FM_RS || W < FM_CT || W % FM_CT || Eh < 1 || Ew < 1) return DGV2_ENOTSUP;
+extern "C" int dgv2_fir_same_mfma_prep(void* bands, int64_t bands_bytes, const int* idx_h, const float* coef_h,
+                                       const int* cnt_h, int Eh, const int* idx_w, const float* coef_w, const int* cnt_w,
+                                       int Ew, int H, int W, int* status, void* stream) {
   const int64_t need = fm_band_bytes(H, W);
-  if (bytes_needed) *bytes_needed = need;
-  if (!bands) return bytes_needed ? 0 : DGV2_EINVAL;
-  if (bands_bytes < need || !aligned16(bands) || !idx_h || !coef_h || !cnt_h || !idx_w || !coef_w || !cnt_w) return DGV2_EINVAL;
+  if (!need || Eh < 1 || Ew < 1) return DGV2_ENOTSUP;
+  if (!bands || bands_bytes < need || !aligned16(bands) || !idx_h || !coef_h || !cnt_h || !idx_w || !coef_w || !cnt_w)
+    return DGV2_EINVAL;
   if (!status) return DGV2_EINVAL;
   FMTabs t{H, W, Eh, Ew, idx_h, coef_h, cnt_h, idx_w, coef_w, cnt_w, status};
   fir_bands_kernel<<<(int)(need / 1024), 64, 0, (hipStream_t)stream>>>((uint4*)bands, t);
@@ -402,17 +415,21 @@ extern "C" int dgv2_fir_same_mfma_q8(void* y8, const void* x, const void* bands,
 }
 
 // dgv2_resample_tab_actbwd for the same-size case on the MFMA kernel: y = R(x) * (ref > 0 ? 1 : alpha) * scale and
-// gb[c] = sum of the stored y.  scratch fp32 [>= *blocks_needed * C]; a call with scratch == NULL only reports
-// *blocks_needed.  Coverage as dgv2_fir_same_mfma.
-extern "C" int dgv2_fir_same_mfma_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, int64_t* blocks_needed,
-                                         const void* x, const void* ref, const void* bands, int B, int C, int H, int W,
-                                         float alpha, float scale, void* stream) {
-  if (!fm_covers(B, C, H, W)) return DGV2_ENOTSUP;
-  const int64_t blocks = (int64_t)B * (W / FM_CT);
-  if (blocks_needed) *blocks_needed = blocks;
-  if (!scratch) return blocks_needed ? 0 : DGV2_EINVAL;
-  if (!y || !gb || !x || !ref || !bands) return DGV2_EINVAL;
-  if (scratch_elems < blocks * C || !aligned16(x) || !aligned16(y) || !aligned16(ref) || !aligned16(bands)) return DGV2_EINVAL;
+// gb[c] = sum of the stored y.  scratch fp32 [>= dgv2_fir_same_mfma_actbwd_scratch elements].  Coverage as
+// dgv2_fir_same_mfma.
+extern "C" int dgv2_fir_same_mfma_actbwd_scratch(int64_t* elems, int B, int C, int H, int W) {
+  if (!elems) return DGV2_EINVAL;
+  *elems = fm_actbwd_elems(B, C, H, W);
+  return *elems ? 0 : DGV2_ENOTSUP;
+}
+
+extern "C" int dgv2_fir_same_mfma_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, const void* x,
+                                         const void* ref, const void* bands, int B, int C, int H, int W, float alpha,
+                                         float scale, void* stream) {
+  const int64_t need = fm_actbwd_elems(B, C, H, W);
+  if (!need) return DGV2_ENOTSUP;
+  if (!y || !gb || !scratch || !x || !ref || !bands) return DGV2_EINVAL;
+  if (scratch_elems < need || !aligned16(x) || !aligned16(y) || !aligned16(ref) || !aligned16(bands)) return DGV2_EINVAL;
   FMGeom g{B, C, H, W, 0, (const uint4*)bands, (const bf16_t*)ref, alpha, scale, scratch, nullptr};
   auto kern = fir_same_mfma_kernel<true>;
   if (FM_LDS > 64 * 1024) {
@@ -421,7 +438,7 @@ extern "C" int dgv2_fir_same_mfma_actbwd(void* y, float* gb, float* scratch, int
   }
   hipStream_t st = (hipStream_t)stream;
   kern<<<dim3(W / FM_CT, C / FM_CB, B), 256, FM_LDS, st>>>((bf16_t*)y, (const bf16_t*)x, g);
-  fm_bias_reduce_kernel<<<C, 256, 0, st>>>(gb, scratch, (int)blocks, C);
+  fm_bias_reduce_kernel<<<C, 256, 0, st>>>(gb, scratch, (int)(need / C), C);   // one row per (b, blockIdx.x)
   DGV2_RETURN_LAST();
 }
 

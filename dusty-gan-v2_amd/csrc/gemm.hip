@@ -342,6 +342,36 @@ __global__ __launch_bounds__(256) void small_bias_reduce_kernel(float* __restric
   if (threadIdx.x == 0) gb[c] = s;
 }
 
+// Grid of the head kernels (bmm_nn_small_kernel, head_bwd_kernel): every sample's P pixels split over ~2048 / B blocks
+// of at least 8 pixels per lane.  One plan for dgv2_bmm_nn_small_act, dgv2_head_bwd and their _scratch entries.
+struct SmallPlan {
+  int ppb;        // pixels per block
+  dim3 grid;      // (splits of a sample, B)
+  int64_t nblk;   // = grid.x * grid.y: rows of per-block partial sums
+};
+
+int small_plan(SmallPlan& p, int B, int P, int O, int K, int dtype) {
+  if (B <= 0 || P <= 0 || O <= 0 || K <= 0) return DGV2_EINVAL;
+  const int vn = dtype == DGV2_BF16 ? 8 : (dtype == DGV2_F32 ? 4 : 0);
+  if (!vn) return DGV2_EINVAL;
+  if (O > 4 || K % vn || 256 % (K / vn)) return DGV2_ENOTSUP;
+  const int lanes = 256 / (K / vn);
+  int nsplit = (2048 + B - 1) / B;
+  const int minpix = lanes * 8;
+  if ((int64_t)nsplit * minpix > P) nsplit = (P + minpix - 1) / minpix;
+  nsplit = nsplit < 1 ? 1 : nsplit;
+  p.ppb = (P + nsplit - 1) / nsplit;
+  p.grid = dim3((P + p.ppb - 1) / p.ppb, B);
+  p.nblk = (int64_t)p.grid.x * p.grid.y;
+  return 0;
+}
+
+// fp32 workspace of dgv2_bmm_nn_small_act: per block the partials of gb [K]
+int64_t small_act_elems(const SmallPlan& p, int K) { return p.nblk * K; }
+
+// fp32 workspace of dgv2_head_bwd: per block the partials of gb_up [K], gw [O, K] and gbh [O], in that order
+int64_t head_bwd_elems(const SmallPlan& p, int O, int K) { return p.nblk * ((int64_t)K + (int64_t)O * K + O); }
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -480,30 +510,31 @@ __global__ __launch_bounds__(256) void head_bwd_reduce_kernel(float* __restrict_
 }  // namespace
 
 // See the section comment above.  gyf fp32 [B, P, O], cvec fp32 [O], w [B, K, O] / resid / ref / y [B, P, K] in `dtype`;
-// gb_up fp32 [K], gw fp32 [B, O, K], gbh fp32 [O] (all overwritten).  scratch: fp32 [>= *blocks_needed * (K + O K + O)];
-// y == NULL with blocks_needed: query only.  DGV2_ENOTSUP: O > 4, K not a multiple of the 16-byte vector or K / vector not
-// dividing 256 (callers then run the separate launches).
+// gb_up fp32 [K], gw fp32 [B, O, K], gbh fp32 [O] (all overwritten).  scratch: fp32 [>= dgv2_head_bwd_scratch elements].
+// DGV2_ENOTSUP: O > 4, K not a multiple of the 16-byte vector or K / vector not dividing 256 (callers then run the
+// separate launches).
+extern "C" int dgv2_head_bwd_scratch(int64_t* elems, int B, int P, int O, int K, int dtype) {
+  if (!elems) return DGV2_EINVAL;
+  *elems = 0;
+  SmallPlan p;
+  const int rc = small_plan(p, B, P, O, K, dtype);
+  if (rc == 0) *elems = head_bwd_elems(p, O, K);
+  return rc;
+}
+
 extern "C" int dgv2_head_bwd(void* y, float* gw, float* gbh, float* gb_up, float* scratch, int64_t scratch_elems,
-                             int64_t* blocks_needed, const float* gyf, const float* cvec, const void* w, const void* resid,
-                             const void* ref, const float* row_scale, float alpha, float ascale, int B, int P, int O, int K,
-                             int dtype, void* stream) {
-  if (B <= 0 || P <= 0 || O <= 0 || K <= 0) return DGV2_EINVAL;
-  const int vn = dtype == DGV2_BF16 ? 8 : (dtype == DGV2_F32 ? 4 : 0);
-  if (!vn) return DGV2_EINVAL;
-  if (O > 4 || K % vn || 256 % (K / vn)) return DGV2_ENOTSUP;
-  const int lanes = 256 / (K / vn);
-  int nsplit = (2048 + B - 1) / B;
-  const int minpix = lanes * 8;
-  if ((int64_t)nsplit * minpix > P) nsplit = (P + minpix - 1) / minpix;
-  nsplit = nsplit < 1 ? 1 : nsplit;
-  const int ppb = (P + nsplit - 1) / nsplit;
-  dim3 grid((P + ppb - 1) / ppb, B);
-  const int64_t nblk = (int64_t)grid.x * grid.y;
-  if (blocks_needed) *blocks_needed = nblk;
-  if (blocks_needed && !y) return 0;   // query only
+                             const float* gyf, const float* cvec, const void* w, const void* resid, const void* ref,
+                             const float* row_scale, float alpha, float ascale, int B, int P, int O, int K, int dtype,
+                             void* stream) {
+  SmallPlan p;
+  const int rc = small_plan(p, B, P, O, K, dtype);
+  if (rc) return rc;
   if (!y || !gw || !gbh || !gb_up || !scratch || !gyf || !cvec || !w || !ref) return DGV2_EINVAL;
-  if (scratch_elems < nblk * ((int64_t)K + (int64_t)O * K + O)) return DGV2_EINVAL;
+  if (scratch_elems < head_bwd_elems(p, O, K)) return DGV2_EINVAL;
   if (!aligned16(y) || !aligned16(ref) || (resid && !aligned16(resid))) return DGV2_ENOTSUP;
+  const int ppb = p.ppb;
+  const dim3 grid = p.grid;
+  const int64_t nblk = p.nblk;
   hipStream_t st = (hipStream_t)stream;
   float* p_gb = scratch;
   float* p_gw = p_gb + nblk * K;
@@ -524,35 +555,34 @@ extern "C" int dgv2_head_bwd(void* y, float* gw, float* gbh, float* gb_up, float
 // 16-byte vector with K / vector dividing 256.  DGV2_ENOTSUP otherwise (use dgv2_bmm_nn_sq).
 extern "C" int dgv2_bmm_nn_small(void* y, const void* x, const void* w, const void* resid, int B, int P, int O, int K,
                                  int dtype, void* stream) {
-  return dgv2_bmm_nn_small_act(y, x, w, resid, B, P, O, K, nullptr, nullptr, 1.f, 1.f, nullptr, nullptr, 0, nullptr, dtype,
-                               stream);
+  return dgv2_bmm_nn_small_act(y, x, w, resid, B, P, O, K, nullptr, nullptr, 1.f, 1.f, nullptr, nullptr, 0, dtype, stream);
 }
 
 // ... followed (ref != NULL) by the activation backward of the upstream layer that produced this operator's input:
 //   y = (x.w^T + resid) * (ref > 0 ? 1 : alpha) * ascale * row_scale[k],  gb[k] = column sums of the unscaled result.
-// scratch: fp32 [>= *blocks_needed * K]; scratch == NULL only reports *blocks_needed.
+// scratch (with ref): fp32 [>= dgv2_bmm_nn_small_act_scratch elements], one row of K partial sums per block.
+extern "C" int dgv2_bmm_nn_small_act_scratch(int64_t* elems, int B, int P, int O, int K, int dtype) {
+  if (!elems) return DGV2_EINVAL;
+  *elems = 0;
+  SmallPlan p;
+  const int rc = small_plan(p, B, P, O, K, dtype);
+  if (rc == 0) *elems = small_act_elems(p, K);
+  return rc;
+}
+
 extern "C" int dgv2_bmm_nn_small_act(void* y, const void* x, const void* w, const void* resid, int B, int P, int O, int K,
                                      const void* ref, const float* row_scale, float alpha, float ascale, float* gb,
-                                     float* scratch, int64_t scratch_elems, int64_t* blocks_needed, int dtype,
-                                     void* stream) {
-  if (B <= 0 || P <= 0 || O <= 0 || K <= 0) return DGV2_EINVAL;
-  if (!blocks_needed && (!y || !x || !w)) return DGV2_EINVAL;
-  const int vn = dtype == DGV2_BF16 ? 8 : (dtype == DGV2_F32 ? 4 : 0);
-  if (!vn) return DGV2_EINVAL;
-  if (O > 4 || K % vn || 256 % (K / vn) || !aligned16(y) || (resid && !aligned16(resid))) return DGV2_ENOTSUP;
+                                     float* scratch, int64_t scratch_elems, int dtype, void* stream) {
+  SmallPlan p;
+  const int rc = small_plan(p, B, P, O, K, dtype);
+  if (rc == DGV2_EINVAL || !y || !x || !w) return DGV2_EINVAL;
+  if (rc || !aligned16(y) || (resid && !aligned16(resid))) return DGV2_ENOTSUP;
   hipStream_t st = (hipStream_t)stream;
-  const int lanes = 256 / (K / vn);
-  int nsplit = (2048 + B - 1) / B;
-  const int minpix = lanes * 8;
-  if ((int64_t)nsplit * minpix > P) nsplit = (P + minpix - 1) / minpix;
-  nsplit = nsplit < 1 ? 1 : nsplit;
-  const int ppb = (P + nsplit - 1) / nsplit;
-  dim3 grid((P + ppb - 1) / ppb, B);
-  const int64_t nblk = (int64_t)grid.x * grid.y;
-  if (blocks_needed) *blocks_needed = nblk;
-  if (blocks_needed && !y) return 0;   // query only
+  const int ppb = p.ppb;
+  const dim3 grid = p.grid;
+  const int64_t nblk = p.nblk;
   if (ref) {
-    if (!gb || !scratch || scratch_elems < nblk * K || !aligned16(ref)) return DGV2_EINVAL;
+    if (!gb || !scratch || scratch_elems < small_act_elems(p, K) || !aligned16(ref)) return DGV2_EINVAL;
     DGV2_DISPATCH_DTYPE(dtype, {
       switch (O) {
         case 1: bmm_nn_small_kernel<T, 1, true><<<grid, 256, 0, st>>>((T*)y, (const T*)x, (const T*)w, (const T*)resid, P, K, ppb, (const T*)ref, row_scale, alpha, ascale, scratch); break;

@@ -419,31 +419,35 @@ __global__ __launch_bounds__(512, 2) void modconv_pe_fwd_kernel(bf16_t* __restri
   }
 }
 
+// Grid of one launch: `tiles` pixel tiles of TP = 128 * NFW pixels, `slabs` slabs of MF * 16 output channels, and the
+// batch in `nsplit` parts of `samples_per_block` samples.  One resident block per CU (the PE fragments fill the register
+// file): one round of blocks, as few sample splits (= PE reloads) as that allows.
+struct MPPlan {
+  int tiles, slabs, nsplit, samples_per_block;
+};
+
+MPPlan mp_plan(int B, int P, int O, int MF, int NFW) {
+  static const int target = getenv("DGV2_MP_BLOCKS") ? atoi(getenv("DGV2_MP_BLOCKS")) : 256;
+  const int TP = 8 * 16 * NFW;
+  MPPlan p;
+  p.tiles = (P + TP - 1) / TP;
+  p.slabs = O / (MF * 16);   // host-checked: a whole number
+  // with several slabs fewer sample splits are needed to fill the chip
+  const int per_split = p.tiles * p.slabs;
+  int nsplit = (target + per_split - 1) / per_split;
+  nsplit = nsplit < 1 ? 1 : (nsplit > B ? B : nsplit);
+  p.samples_per_block = (B + nsplit - 1) / nsplit;
+  p.nsplit = (B + p.samples_per_block - 1) / p.samples_per_block;
+  return p;
+}
+
 template <int MF, int NFW, int KA, int KS, bool HEAD = false, bool ACTBWD = false>
 int mp_launch(void* y, const void* xa, const void* xs, const void* w, MPGeom g, hipStream_t st, int sumsq_cap,
-              int* sumsq_used, int64_t* part_rows = nullptr, int64_t part_cap = 0) {
-  constexpr int TP = 8 * 16 * NFW;
-  const int tiles = (g.P + TP - 1) / TP;
-  // one resident block per CU (the PE fragments fill the register file): one round of blocks, as few sample
-  // splits (= PE reloads) as that allows
-  static const int target = getenv("DGV2_MP_BLOCKS") ? atoi(getenv("DGV2_MP_BLOCKS")) : 256;
-  int nsplit = (target + tiles - 1) / tiles;
-  nsplit = nsplit < 1 ? 1 : (nsplit > g.B ? g.B : nsplit);
-  g.samples_per_block = (g.B + nsplit - 1) / nsplit;
-  nsplit = (g.B + g.samples_per_block - 1) / g.samples_per_block;
-  const int slabs = g.O / (MF * 16);   // host-checked: a whole number
-  // with several slabs fewer sample splits are needed to fill the chip
-  if (slabs > 1) {
-    nsplit = (target + tiles * slabs - 1) / (tiles * slabs);
-    nsplit = nsplit < 1 ? 1 : (nsplit > g.B ? g.B : nsplit);
-    g.samples_per_block = (g.B + nsplit - 1) / nsplit;
-    nsplit = (g.B + g.samples_per_block - 1) / g.samples_per_block;
-  }
+              int* sumsq_used) {
+  const MPPlan pl = mp_plan(g.B, g.P, g.O, MF, NFW);
+  const int tiles = pl.tiles, slabs = pl.slabs, nsplit = pl.nsplit;
+  g.samples_per_block = pl.samples_per_block;
   dim3 grid(tiles * slabs, nsplit);
-  if (ACTBWD) {   // rows of column-sum partials this launch writes; a query (part_cap == 0) launches nothing
-    if (part_rows) *part_rows = (int64_t)tiles * nsplit;
-    if (part_cap < (int64_t)tiles * nsplit) return part_cap == 0 ? 0 : DGV2_EINVAL;
-  }
   if (g.sumsq && sumsq_used && tiles * nsplit * slabs <= sumsq_cap) *sumsq_used = tiles * nsplit * slabs;
   else g.sumsq = nullptr;
   constexpr size_t lds = sizeof(uint4) * 2 * (size_t)(((MF * 16) * (KA + KS) * 4 + 511) / 512 * 512);
@@ -469,7 +473,28 @@ __global__ __launch_bounds__(256) void mp_gb_reduce_kernel(float* __restrict__ g
   if (threadIdx.x == 0) gb[c] = s;
 }
 
+// dgv2_modconv_pe_dgrad_actbwd: rows of K column-sum partials its launch writes, one per (sample split, pixel tile) -- both
+// of its instances (MF = K / 16, NFW = 2) cover K in one slab.  DGV2_ENOTSUP outside K in {32, 64}, bf16.
+// (K = 128 / 256, levels 2 / 1: their instances have no registers left for the prefetched upstream outputs and the
+// column sums -- 27 / 44 spills; they gained 6 us as a single-buffered form and keep the two launches)
+int mp_dgrad_actbwd_rows(int64_t* rows, int B, int P, int K, int dtype) {
+  if (dtype != DGV2_BF16 || (K != 32 && K != 64)) return DGV2_ENOTSUP;
+  if (B <= 0 || P <= 0) return DGV2_EINVAL;
+  const MPPlan pl = mp_plan(B, P, K, K / 16, 2);
+  *rows = (int64_t)pl.tiles * pl.nsplit;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int dgv2_modconv_pe_dgrad_actbwd_scratch(int64_t* elems, int B, int P, int K, int dtype) {
+  if (!elems) return DGV2_EINVAL;
+  *elems = 0;
+  int64_t rows;
+  const int rc = mp_dgrad_actbwd_rows(&rows, B, P, K, dtype);
+  if (rc == 0) *elems = rows * K;
+  return rc;
+}
 
 // Data gradient of a PE-free modulated 1x1 layer (conv2 of a generator level: K -> K channels) FUSED with the activation
 // backward of the layer that produced its input (conv1 of the level):
@@ -479,20 +504,18 @@ __global__ __launch_bounds__(256) void mp_gb_reduce_kernel(float* __restrict__ g
 // -- bit for bit the pair dgv2_modconv_pe_fwd_sq (Ks = 0) + dgv2_bias_act_bwd_rs it replaces (one pass over the gradient
 // instead of three; reference: the autograd chain of ModConv2d -> FusedLeakyReLU, gans/models/ops/style.py:105-118,
 // fused_act.py:46-59).  gy [B,P,K], wt [B,K,K] (conv2's per-sample weights, transposed), yref [B,P,K] bf16; up_scale, gb
-// fp32 [K]; scratch fp32 [scratch_elems] >= *rows_needed * K (call with scratch == NULL to query rows_needed; nothing is
-// launched).  K in {32, 64} (generator levels 4 / 3); DGV2_ENOTSUP otherwise.
-extern "C" int dgv2_modconv_pe_dgrad_actbwd(void* gpre, float* gb, float* scratch, int64_t scratch_elems, int64_t* rows_needed,
-                                            const void* gy, const void* wt, const void* yref, const float* up_scale,
-                                            float alpha, float scale, int B, int P, int K, int dtype, void* stream) {
-  if (rows_needed) *rows_needed = 0;
-  // (K = 128 / 256, levels 2 / 1: their instances have no registers left for the prefetched upstream outputs and the
-  // column sums -- 27 / 44 spills; they gained 6 us as a single-buffered form and keep the two launches)
-  if (dtype != DGV2_BF16 || (K != 32 && K != 64)) return DGV2_ENOTSUP;
-  if (B <= 0 || P <= 0) return DGV2_EINVAL;
-  const bool query = scratch == nullptr;
-  if (!query && (!gpre || !gb || !gy || !wt || !yref || !up_scale || !aligned16(gpre) || !aligned16(gy) || !aligned16(wt) ||
-                 !aligned16(yref)))
+// fp32 [K]; scratch fp32 [>= dgv2_modconv_pe_dgrad_actbwd_scratch elements].  K in {32, 64} (generator levels 4 / 3);
+// DGV2_ENOTSUP otherwise.
+extern "C" int dgv2_modconv_pe_dgrad_actbwd(void* gpre, float* gb, float* scratch, int64_t scratch_elems, const void* gy,
+                                            const void* wt, const void* yref, const float* up_scale, float alpha,
+                                            float scale, int B, int P, int K, int dtype, void* stream) {
+  int64_t rows;
+  const int rc = mp_dgrad_actbwd_rows(&rows, B, P, K, dtype);
+  if (rc) return rc;
+  if (!gpre || !gb || !scratch || !gy || !wt || !yref || !up_scale || !aligned16(gpre) || !aligned16(gy) || !aligned16(wt) ||
+      !aligned16(yref))
     return DGV2_EINVAL;
+  if (scratch_elems < rows * K) return DGV2_EINVAL;
 #ifdef DGV2_ABLATE
   MPGeom g{B, P, K, 0, K, K, 1, 0, nullptr, 0, alpha, scale, nullptr, nullptr, nullptr, nullptr};
 #else
@@ -502,14 +525,10 @@ extern "C" int dgv2_modconv_pe_dgrad_actbwd(void* gpre, float* gb, float* scratc
   g.up_scale = up_scale;
   g.gbpart = scratch;
   hipStream_t st = (hipStream_t)stream;
-  int64_t rows = 0;
-  const int64_t cap = query ? 0 : scratch_elems / K;
-  if (!query && cap < 1) return DGV2_EINVAL;
-  int rc;
-  if (K == 32) rc = mp_launch<2, 2, 1, 0, false, true>(gpre, gy, gy, wt, g, st, 0, nullptr, &rows, cap);
-  else rc = mp_launch<4, 2, 2, 0, false, true>(gpre, gy, gy, wt, g, st, 0, nullptr, &rows, cap);
-  if (rows_needed) *rows_needed = rows;
-  if (rc || query) return rc;
+  int lrc;
+  if (K == 32) lrc = mp_launch<2, 2, 1, 0, false, true>(gpre, gy, gy, wt, g, st, 0, nullptr);
+  else lrc = mp_launch<4, 2, 2, 0, false, true>(gpre, gy, gy, wt, g, st, 0, nullptr);
+  if (lrc) return lrc;
   mp_gb_reduce_kernel<<<K, 256, 0, st>>>(gb, scratch, (int)rows, K);
   DGV2_RETURN_LAST();
 }

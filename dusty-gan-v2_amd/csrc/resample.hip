@@ -538,36 +538,64 @@ __global__ __launch_bounds__(256) void rs_bias_reduce_kernel(float* __restrict__
 
 }  // namespace
 
+namespace {
+
+// Strip height, block count and fp32 workspace (one row of C partial bias sums per block) of dgv2_resample_tab_actbwd:
+// the one place that knows them.  DGV2_ENOTSUP where the streaming kernel does not cover what is seen of the geometry here.
+struct RsActPlan {
+  int SH;
+  int64_t blocks, elems;
+};
+
+int rs_actbwd_plan(RsActPlan& p, int B, int C, int out_h, int out_w, int Eh, int dtype) {
+  if (B <= 0 || C <= 0 || out_h <= 0 || out_w <= 0 || Eh <= 0) return DGV2_EINVAL;
+  const int vn = dtype == DGV2_BF16 ? 8 : (dtype == DGV2_F32 ? 4 : 0);
+  if (!vn) return DGV2_EINVAL;
+  if (C % vn || 256 % (C / vn) || Eh > 64) return DGV2_ENOTSUP;
+  p.SH = out_h >= 32 ? 16 : (out_h >= 8 ? 8 : out_h);
+  while (p.SH > 1 && p.SH * Eh > 64) p.SH >>= 1;
+  p.blocks = (int64_t)B * ((out_h + p.SH - 1) / p.SH) * (((int64_t)out_w * (C / vn) + 255) / 256);
+  if (p.blocks >= (1LL << 31)) return DGV2_ENOTSUP;
+  p.elems = p.blocks * C;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int dgv2_resample_tab_actbwd_scratch(int64_t* elems, int B, int C, int out_h, int out_w, int Eh, int dtype) {
+  if (!elems) return DGV2_EINVAL;
+  *elems = 0;
+  RsActPlan p;
+  const int rc = rs_actbwd_plan(p, B, C, out_h, out_w, Eh, dtype);
+  if (rc == 0) *elems = p.elems;
+  return rc;
+}
+
 // Resampling (normally the ADJOINT tables of a blur/down) followed by the backward of a fused bias + leaky-ReLU:
 //   y = R(x) * (ref > 0 ? 1 : alpha) * scale,   gb[c] = sum of y over everything but the channel   (fp32 [C])
 // ref: forward output of the activation, [B, out_h, out_w, C] contiguous like y (ldy == C).  scratch: fp32
-// [>= blocks * C] with blocks = *blocks_needed reported when scratch is NULL (query call: nothing is launched).
+// [>= dgv2_resample_tab_actbwd_scratch elements].
 // Returns DGV2_ENOTSUP when the streaming kernel does not cover the geometry (callers run dgv2_resample_tab_sq and
 // dgv2_bias_act_bwd_rs).  replaces: Resample adjoint (common.py:105-135) + FusedLeakyReLUFunctionBackward
 // (fused_act.py:22-45) of the discriminator's conv1 -> activation -> blur/down chain (dusty_v2.py:325-345).
-extern "C" int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, int64_t* blocks_needed,
-                                        const void* x, const void* ref, const int* idx_h, const float* coef_h,
-                                        const int* cnt_h, int Eh, const int* idx_w, const float* coef_w,
-                                        const int* cnt_w, int Ew, int B, int C, int in_h, int in_w, int out_h,
-                                        int out_w, float alpha, float scale, int dtype, void* stream) {
-  if (B <= 0 || C <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 || Eh <= 0 || Ew <= 0) return DGV2_EINVAL;
-  const int vn = dtype == DGV2_BF16 ? 8 : (dtype == DGV2_F32 ? 4 : 0);
-  if (!vn) return DGV2_EINVAL;
-  if (C % vn || 256 % (C / vn) || Ew > 4 || Eh > 64) return DGV2_ENOTSUP;
-  int SH = out_h >= 32 ? 16 : (out_h >= 8 ? 8 : out_h);
-  while (SH > 1 && SH * Eh > 64) SH >>= 1;
-  const int64_t blocks = (int64_t)B * ((out_h + SH - 1) / SH) * (((int64_t)out_w * (C / vn) + 255) / 256);
-  if (blocks >= (1LL << 31)) return DGV2_ENOTSUP;
-  if (blocks_needed) *blocks_needed = blocks;
-  if (!scratch) return blocks_needed ? 0 : DGV2_EINVAL;
-  if (!y || !gb || !x || !ref || !idx_h || !coef_h || !cnt_h || !idx_w || !coef_w || !cnt_w) return DGV2_EINVAL;
-  if (scratch_elems < blocks * C || !aligned16(x) || !aligned16(y) || !aligned16(ref)) return DGV2_EINVAL;
+extern "C" int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, const void* x,
+                                        const void* ref, const int* idx_h, const float* coef_h, const int* cnt_h, int Eh,
+                                        const int* idx_w, const float* coef_w, const int* cnt_w, int Ew, int B, int C,
+                                        int in_h, int in_w, int out_h, int out_w, float alpha, float scale, int dtype,
+                                        void* stream) {
+  if (in_h <= 0 || in_w <= 0 || Ew <= 0) return DGV2_EINVAL;
+  RsActPlan p;
+  const int rc = rs_actbwd_plan(p, B, C, out_h, out_w, Eh, dtype);
+  if (rc) return rc;
+  if (Ew > 4) return DGV2_ENOTSUP;
+  if (!y || !gb || !scratch || !x || !ref || !idx_h || !coef_h || !cnt_h || !idx_w || !coef_w || !cnt_w) return DGV2_EINVAL;
+  if (scratch_elems < p.elems || !aligned16(x) || !aligned16(y) || !aligned16(ref)) return DGV2_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   DGV2_DISPATCH_DTYPE(dtype, {
-    rs_launch_act<T>(Ew, (int)blocks, st, (T*)y, (const T*)x, idx_h, coef_h, cnt_h, Eh, idx_w, coef_w, cnt_w, B, C, C, C,
-                     in_h, in_w, out_h, out_w, SH, (const T*)ref, alpha, scale, scratch);
+    rs_launch_act<T>(Ew, (int)p.blocks, st, (T*)y, (const T*)x, idx_h, coef_h, cnt_h, Eh, idx_w, coef_w, cnt_w, B, C, C, C,
+                     in_h, in_w, out_h, out_w, p.SH, (const T*)ref, alpha, scale, scratch);
   });
-  rs_bias_reduce_kernel<<<C, 256, 0, st>>>(gb, scratch, (int)blocks, C);
+  rs_bias_reduce_kernel<<<C, 256, 0, st>>>(gb, scratch, (int)p.blocks, C);
   DGV2_RETURN_LAST();
 }
 

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE
 
 F32, BF16 = 0, 1
 F16 = 3   # the dgv2_seg_loss_* entries and dgv2_fire_fwd only
-ABI_VERSION = 57
+ABI_VERSION = 58
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -66,7 +66,8 @@ SIGNATURES = {
     "dgv2_emd_matchcost": [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr],
     "dgv2_emd_matchcost_grad": [_c_ptr] * 5 + [_c_int] * 3 + [_c_ptr],
     "dgv2_nsgan_loss": [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_f32, _c_ptr, _c_ptr, _c_ptr],
-    "dgv2_modconv_pe_dgrad_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64] + [_c_ptr] * 5 + [_c_f32, _c_f32] + [_c_int] * 4 + [_c_ptr],
+    "dgv2_modconv_pe_dgrad_actbwd_scratch": [_c_ptr] + [_c_int] * 4,
+    "dgv2_modconv_pe_dgrad_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64] + [_c_ptr] * 4 + [_c_f32, _c_f32] + [_c_int] * 4 + [_c_ptr],
     "dgv2_colmean_lerp": [_c_ptr, _c_ptr, _c_int, _c_int, _c_i64, _c_f32, _c_ptr],
     "dgv2_d_tail_fwd": [_c_ptr] * 6 + [_c_int, _c_int] + [_c_f32] * 4 + [_c_ptr],
     "dgv2_d_tail_bwd": [_c_ptr] * 7 + [_c_int, _c_int] + [_c_f32] * 4 + [_c_ptr],
@@ -81,12 +82,14 @@ SIGNATURES = {
     "dgv2_conv_taps_fp8": [_c_ptr] * 4 + [_c_int] * 14 + [_c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_ptr],
     "dgv2_modconv_up_t": [_c_ptr] * 5 + [_c_f32] + [_c_int] * 9 + [_c_ptr],
     "dgv2_up2_lag_sumsq": [_c_ptr] * 5 + [_c_int] * 5 + [_c_ptr, _c_int, _c_ptr, _c_ptr],
-    "dgv2_resample_tab_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr] + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3
+    "dgv2_resample_tab_actbwd_scratch": [_c_ptr] + [_c_int] * 6,
+    "dgv2_resample_tab_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3
                                 + [_c_int] * 7 + [_c_f32, _c_f32, _c_int, _c_ptr],
-    "dgv2_fir_same_mfma_prep": [_c_ptr, _c_i64, _c_ptr] + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr, _c_ptr],
+    "dgv2_fir_same_mfma_prep_scratch": [_c_ptr, _c_int, _c_int],
+    "dgv2_fir_same_mfma_prep": [_c_ptr, _c_i64] + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr, _c_ptr],
     "dgv2_fir_same_mfma": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr],
-    "dgv2_fir_same_mfma_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_int] * 4
-                                 + [_c_f32, _c_f32, _c_ptr],
+    "dgv2_fir_same_mfma_actbwd_scratch": [_c_ptr] + [_c_int] * 4,
+    "dgv2_fir_same_mfma_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr] + [_c_int] * 4 + [_c_f32, _c_f32, _c_ptr],
     "dgv2_resample_tab_sq": [_c_ptr] * 5 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 10 + [_c_ptr, _c_int, _c_ptr, _c_ptr],
     "dgv2_bmm_tn_cat": [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr],
     "dgv2_lerp_list": [_c_ptr] * 3 + [_c_int, _c_f32, _c_ptr],
@@ -97,10 +100,11 @@ SIGNATURES = {
     "dgv2_ema_scalar": [_c_ptr] * 3 + [_c_int] + [_c_f32] * 3 + [_c_int, _c_ptr, _c_int, _c_ptr],
     "dgv2_ema_scalar_group": [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_int] + [_c_f32] * 3 + [_c_int, _c_ptr, _c_ptr],
     "dgv2_bmm_nn_small": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr],
-    "dgv2_bmm_nn_small_act": [_c_ptr] * 4 + [_c_int] * 4 + [_c_ptr, _c_ptr, _c_f32, _c_f32, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_int,
-                              _c_ptr],
+    "dgv2_bmm_nn_small_act_scratch": [_c_ptr] + [_c_int] * 5,
+    "dgv2_bmm_nn_small_act": [_c_ptr] * 4 + [_c_int] * 4 + [_c_ptr, _c_ptr, _c_f32, _c_f32, _c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr],
     "dgv2_bmm_tn_small": [_c_ptr] * 3 + [_c_int] * 5 + [_c_ptr],
-    "dgv2_head_bwd": [_c_ptr] * 5 + [_c_i64] + [_c_ptr] * 7 + [_c_f32, _c_f32] + [_c_int] * 5 + [_c_ptr],
+    "dgv2_head_bwd_scratch": [_c_ptr] + [_c_int] * 5,
+    "dgv2_head_bwd": [_c_ptr] * 5 + [_c_i64] + [_c_ptr] * 6 + [_c_f32, _c_f32] + [_c_int] * 5 + [_c_ptr],
     "dgv2_transpose_list": [_c_ptr] * 5 + [_c_int] * 3 + [_c_ptr],
     "dgv2_mod_prep_all_fwd": [_c_ptr] * 13 + [_c_ptr, _c_int, _c_int, _c_ptr],
     "dgv2_mod_prep_all_bwd": [_c_ptr, _c_i64] + [_c_ptr] * 15 + [_c_ptr, _c_int, _c_int, _c_ptr, _c_i64, _c_ptr],
@@ -253,6 +257,25 @@ def try_call(name, *args):
     if rc != 0:
         raise RuntimeError(f"{name} failed with code {rc}")
     return True
+
+
+_scratch_memo = {}
+
+
+def scratch_elems(entry, *args):
+    """What the host-only `entry` (a `<kernel entry>_scratch` of include/dgv2.h, "Workspaces") reports for the geometry
+    `args`: the size of that kernel's workspace, or 0 where it answers DGV2_ENOTSUP (the kernel does not take the
+    geometry; dgv2_fps needs none).  Any other code raises like call().  Lists / tuples of ints go over as int arrays.
+    The library is asked once per distinct (entry, args)."""
+    key = (entry, tuple(tuple(a) if isinstance(a, (list, tuple)) else a for a in args))
+    n = _scratch_memo.get(key)
+    if n is None:
+        out = ctypes.c_int64(0)
+        rc = getattr(lib, entry)(ctypes.addressof(out), *[int_array(a) if isinstance(a, tuple) else a for a in key[1]])
+        if rc not in (0, ENOTSUP):
+            raise RuntimeError(f"{entry} failed with code {rc}")
+        n = _scratch_memo[key] = 0 if rc else out.value
+    return n
 
 
 # ---------------------------------------------------------------------------------------

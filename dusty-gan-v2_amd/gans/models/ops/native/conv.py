@@ -314,9 +314,6 @@ _WGRAD_DIRECT_MAXC = int(os.environ.get("DGV2_WGRAD_DIRECT_MAXC", "64"))
 _WGRAD_STREAM = os.environ.get("DGV2_NO_WGRAD_STREAM") is None   # A/B switch for benchmarking
 
 
-_WGRAD_SCRATCH = {}
-
-
 _TN_STREAM = os.environ.get("DGV2_NO_TN_STREAM") is None           # A/B switch for benchmarking
 
 
@@ -354,12 +351,8 @@ def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
         x3 = int(_X3_AUTO[1].get(C, C))
     if (x3 and _CONV_X3 and x.dtype == torch.float32 and g.ring3x3 and g.stride == 1
             and O % 128 == 0 and C >= 64 and C % 8 == 0 and W % 32 == 0 and 0 <= x3 - C // 64 * 64 <= 16):
-        key = ("x3", B, H, W, C, int(x3), O)
-        if key not in _WGRAD_SCRATCH:
-            n = _ct.c_int64(0)
-            N.call("dgv2_conv3x3_x3_wgrad_scratch", _ct.addressof(n), B, H, W, C, int(x3), O)
-            _WGRAD_SCRATCH[key] = n.value
-        scratch = torch.empty(_WGRAD_SCRATCH[key], device=x.device, dtype=torch.float32)
+        scratch = torch.empty(N.scratch_elems("dgv2_conv3x3_x3_wgrad_scratch", B, H, W, C, int(x3), O), device=x.device,
+                              dtype=torch.float32)
         gw3 = (out if (out is not None and gscale is not None and tuple(out.shape) == (O, C, 3, 3)) else
                torch.empty((O, C, 3, 3) if gscale is not None else (O, 3, 3, C), device=x.device, dtype=torch.float32))
         if N.try_call("dgv2_conv3x3_x3_wgrad", N.ptr(gw3), N.ptr(scratch), scratch.numel(), N.ptr(gy), N.ptr(x), B, H, W, C,
@@ -377,12 +370,8 @@ def _conv_wgrad_raw(gy, x, g, gscale=None, x3=None, xexact=0, out=None):
     else:
         gw = torch.empty((O, g.kh, g.kw, C), device=x.device, dtype=torch.float32)
     if stream_ok:
-        key = (B, H, W, C, O, g.kh, g.stride, g.pad, _dt(x))
-        if key not in _WGRAD_SCRATCH:
-            n = _ct.c_int64(0)
-            N.call("dgv2_conv_wgrad_stream_scratch", _ct.addressof(n), B, H, W, C, O, g.kh, g.stride, g.pad, _dt(x))
-            _WGRAD_SCRATCH[key] = n.value
-        scratch = torch.empty(_WGRAD_SCRATCH[key], device=x.device, dtype=torch.float32)
+        scratch = torch.empty(N.scratch_elems("dgv2_conv_wgrad_stream_scratch", B, H, W, C, O, g.kh, g.stride, g.pad, _dt(x)),
+                              device=x.device, dtype=torch.float32)
         N.call("dgv2_conv_wgrad_stream_pl", N.ptr(gw), N.ptr(scratch), scratch.numel(), N.ptr(gy), N.ptr(x), B, H, W,
                C, O, g.kh, g.stride, g.pad, g.ring, 1.0 if gscale is None else float(gscale), int(gscale is not None),
                _dt(x), N.stream())
@@ -953,9 +942,6 @@ def conv_weight_bank(entries, dtype, image8=None):
     return list(zip(wfs, wts)) if image8 is None else list(zip(wfs, wts, w8s, w8ts))
 
 
-_ACTBWD_BLOCKS = {}
-
-
 _FUSED_ACTBWD = os.environ.get("DGV2_NO_FUSED_ACTBWD") is None   # A/B switch for benchmarking
 
 
@@ -976,21 +962,18 @@ def _resample_actbwd(g, out, spec, in_hw, alpha, scale):
     tabs = (N.ptr(bands),) if mfma else tabs
     geo = (B, C, H, W) if mfma else (B, C, Ho, Wo, H, W)
     tail = (alpha, scale) if mfma else (alpha, scale, _dt(g))
-    key = (entry, B, H, W, C, Eh, Ew, _dt(g))
-    if key not in _ACTBWD_BLOCKS:
-        nb = _ct.c_int64(0)
-        ok = N.try_call(entry, None, None, None, 0, _ct.addressof(nb), None, None, *tabs, *geo, *tail, N.stream())
-        _ACTBWD_BLOCKS[key] = nb.value if ok else 0
-    nblk = _ACTBWD_BLOCKS[key]
-    if nblk == 0:
+    if mfma:
+        need = N.scratch_elems(entry + "_scratch", B, C, H, W)
+    else:   # (Ew > 4: the kernel entry alone refuses it, the size does not depend on Ew)
+        need = N.scratch_elems(entry + "_scratch", B, C, H, W, Eh, _dt(g)) if Ew <= 4 else 0
+    if need == 0:
         return None
     g = g.contiguous()
     N.check(g, out)
     gpre = torch.empty_like(out)
     gb = torch.empty(C, device=g.device, dtype=torch.float32)
-    scratch = torch.empty(nblk * C, device=g.device, dtype=torch.float32)
-    N.call(entry, N.ptr(gpre), N.ptr(gb), N.ptr(scratch), scratch.numel(), None, N.ptr(g), N.ptr(out), *tabs, *geo, *tail,
-           N.stream())
+    scratch = torch.empty(need, device=g.device, dtype=torch.float32)
+    N.call(entry, N.ptr(gpre), N.ptr(gb), N.ptr(scratch), scratch.numel(), N.ptr(g), N.ptr(out), *tabs, *geo, *tail, N.stream())
     return gpre, gb
 
 

@@ -4,8 +4,6 @@ semseg/models/crf_as_rnn.py:110-132) as one autograd node over dgv2_crf_rnn_forw
 
 Part of gans.models.ops.native (wrappers around the libdgv2 C ABI, see the package docstring).  First order only.
 """
-import ctypes as _ct
-
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -46,12 +44,11 @@ class _CRFRNN(torch.autograd.Function):
         kh, kw = kg.shape[2:]
         g_out = g_out.float().contiguous()
         N.check(g_out)
-        need = _ct.c_int64(0)
-        N.call("dgv2_crf_rnn_backward_scratch", _ct.addressof(need), B, C, H, W, ctx.num_iters)
-        scratch = torch.empty(need.value, device=unary.device, dtype=torch.float32)
+        scratch = torch.empty(N.scratch_elems("dgv2_crf_rnn_backward_scratch", B, C, H, W, ctx.num_iters), device=unary.device,
+                              dtype=torch.float32)
         g_unary, g_ws, g_wa, g_compat = (torch.empty_like(t) for t in (unary, ws, wa, compat))
         N.call("dgv2_crf_rnn_backward", N.ptr(g_unary), N.ptr(g_ws), N.ptr(g_wa), N.ptr(g_compat), N.ptr(scratch),
-               need.value, N.ptr(g_out), N.ptr(qsave), N.ptr(unary), N.ptr(xyz), N.ptr(mask), N.ptr(kg), N.ptr(ka), N.ptr(tb),
+               scratch.numel(), N.ptr(g_out), N.ptr(qsave), N.ptr(unary), N.ptr(xyz), N.ptr(mask), N.ptr(kg), N.ptr(ka), N.ptr(tb),
                N.ptr(ws), N.ptr(wa), N.ptr(compat), B, C, H, W, kh, kw, ctx.num_iters, N.stream())
         return g_unary, g_ws, g_wa, g_compat, None, None, None, None, None, None
 

@@ -2,7 +2,6 @@
 
 Part of gans.models.ops.native (wrappers around the libdgv2 C ABI; package docstring and DESIGN.md section 27: the import rules).
 """
-import ctypes as _ct
 import math
 import os
 
@@ -22,21 +21,14 @@ from .modgemm import _bmm_nn_raw, bmm_nn_cat_sq_call, bmm_tn_call, bmm_tn_cat_ca
 # act-grad, data gradient, weight gradient, preparation backward (dgv2_mod_prep_bwd).
 # reference: ModConv2d.forward + FusedLeakyReLU, gans/models/ops/style.py:68-126, dusty_v2.py:161-170
 # ---------------------------------------------------------------------------------------
-_TN_SCRATCH = {}
-
-
 def _bmm_tn_stream(g3, xa, B, H, W_, I, O, shared=False, out=None):
     """gw fp32 [B,O,I] = per-sample sum over pixels of gy [B,H*W,O] x xa [B,H,W,I] (dgv2_bmm_tn_stream_ld); shared: xa is
     one image [1,H,W,I] contracted against every sample (the positional encoding).  out: a [B,O,ld] fp32 tensor
     (ld >= I) whose first I columns receive the result in place."""
-    key = (B, H, W_, I, O)
-    if key not in _TN_SCRATCH:
-        n = _ct.c_int64(0)
-        N.call("dgv2_bmm_tn_stream_scratch", _ct.addressof(n), B, H, W_, I, O, _dt(xa))
-        _TN_SCRATCH[key] = n.value
     gw = torch.empty((B, O, I), device=xa.device, dtype=torch.float32) if out is None else out
     ld = 0 if out is None else int(out.shape[2])
-    scratch = torch.empty(_TN_SCRATCH[key], device=xa.device, dtype=torch.float32)
+    scratch = torch.empty(N.scratch_elems("dgv2_bmm_tn_stream_scratch", B, H, W_, I, O, _dt(xa)), device=xa.device,
+                          dtype=torch.float32)
     N.call("dgv2_bmm_tn_stream_ld", N.ptr(gw), ld, N.ptr(scratch), scratch.numel(), N.ptr(g3), N.ptr(xa), int(shared), B, H,
            W_, I, O, _dt(xa), N.stream())
     return gw
@@ -263,12 +255,8 @@ class _ModPrepAll(Function):
             dsaves.append(dflat[off:off + B * m["O"]])
             off += B * m["O"]
         # scratch of the atomic-free form (dgv2.h): per-unit partial sums, folded by the fix-up kernels
-        key = ("prep_all_bwd", tuple((m["O"], m["I"]) for m in lay), B)
-        if key not in _TN_SCRATCH:
-            n = _ct.c_int64(0)
-            N.call("dgv2_mod_prep_all_bwd_scratch", _ct.addressof(n), ints["O"], ints["I"], B, L)
-            _TN_SCRATCH[key] = n.value
-        scratch = torch.empty(_TN_SCRATCH[key], device=dev, dtype=torch.float32)
+        need = N.scratch_elems("dgv2_mod_prep_all_bwd_scratch", [m["O"] for m in lay], [m["I"] for m in lay], B, L)
+        scratch = torch.empty(need, device=dev, dtype=torch.float32)
         N.call("dgv2_mod_prep_all_bwd", N.ptr(flat), flat.numel(), N.ptr_array(outs), N.int_array(ncorr),
                N.ptr_array([Gs[m["group"]] for m in lay]), N.ptr_array(list(Ws)), N.ptr_array(list(Ss)), N.ptr(stats),
                N.ptr(rot_tab), N.ptr_array(dsaves), N.ptr_array([m["fw"] for m in lay]), ints["O"], ints["I"], ints["Otot"],
@@ -476,8 +464,8 @@ def pe_wgrad(g3, xs, out=None, col0=0):
     # P = 8192, O = 64: 68 / 70; P = 2048, O = 128: 41 / 31 (10 us lost there; smaller maps use dgv2_bmm_tn_cat)
     if not (_PE_WGRAD and g3.dtype == torch.bfloat16 and xs.dtype == torch.bfloat16 and (P >= _PE_WGRAD_MINP)):
         return None
-    n = _ct.c_int64(0)
-    if N.lib.dgv2_pe_wgrad_scratch(_ct.byref(n), B, P, O, Ks) != 0 or n.value == 0:
+    need = N.scratch_elems("dgv2_pe_wgrad_scratch", B, P, O, Ks)
+    if need == 0:
         return None
     g3 = g3.contiguous()
     xs = xs.contiguous()
@@ -486,9 +474,9 @@ def pe_wgrad(g3, xs, out=None, col0=0):
         return None
     if out is None:
         out = torch.empty((B, O, Ks), device=g3.device, dtype=torch.float32)
-    scratch = torch.empty(n.value, device=g3.device, dtype=torch.float32)
+    scratch = torch.empty(need, device=g3.device, dtype=torch.float32)
     N.check(g3, xs)
-    N.call("dgv2_pe_wgrad", N.ptr(out), N.ptr(scratch), n.value, N.ptr(g3), N.ptr(xs), B, P, O, Ks, ld, int(col0), N.stream())
+    N.call("dgv2_pe_wgrad", N.ptr(out), N.ptr(scratch), need, N.ptr(g3), N.ptr(xs), B, P, O, Ks, ld, int(col0), N.stream())
     return out
 
 
@@ -533,14 +521,10 @@ def _mod_wgrad(g3, xa, xs, B, H, W_, I, Otot, dt):
     return gwb
 
 
-_HEAD_ACT_BLOCKS = {}
-
-
 _HEAD_ACTBWD = os.environ.get("DGV2_NO_HEAD_ACTBWD") is None   # A/B switch for benchmarking
 
 
 _DGRAD_ACTBWD = os.environ.get("DGV2_NO_DGRAD_ACTBWD") is None   # A/B switch for benchmarking
-_DGRAD_ACT_ROWS = {}
 
 
 def _dgrad_actbwd(g3, wt, xa, up):
@@ -554,22 +538,16 @@ def _dgrad_actbwd(g3, wt, xa, up):
             or K != O or K not in (32, 64) or tuple(wt.shape) != (B, K, O)
             or P < modgemm._PE_FREE_MINP.get((O, K), 1 << 30) or up.get("link") is None):
         return None
-    key = (B, P, K)
-    if key not in _DGRAD_ACT_ROWS:
-        nr = _ct.c_int64(0)
-        ok = N.try_call("dgv2_modconv_pe_dgrad_actbwd", None, None, None, 0, _ct.addressof(nr), None, None, None, None,
-                        1.0, 1.0, B, P, K, N.BF16, N.stream())
-        _DGRAD_ACT_ROWS[key] = nr.value if ok else 0
-    rows = _DGRAD_ACT_ROWS[key]
-    if rows == 0:
+    need = N.scratch_elems("dgv2_modconv_pe_dgrad_actbwd_scratch", B, P, K, N.BF16)
+    if need == 0:
         return None
     g3 = g3.contiguous()
     xr = xa.contiguous()
     gpre = torch.empty((B, P, K), device=xa.device, dtype=xa.dtype)
     gb = torch.empty(K, device=xa.device, dtype=torch.float32)
-    scratch = torch.empty(rows * K, device=xa.device, dtype=torch.float32)
+    scratch = torch.empty(need, device=xa.device, dtype=torch.float32)
     N.check(g3, wt, xr, up["cvec"])
-    if not N.try_call("dgv2_modconv_pe_dgrad_actbwd", N.ptr(gpre), N.ptr(gb), N.ptr(scratch), scratch.numel(), None, N.ptr(g3),
+    if not N.try_call("dgv2_modconv_pe_dgrad_actbwd", N.ptr(gpre), N.ptr(gb), N.ptr(scratch), scratch.numel(), N.ptr(g3),
                       N.ptr(wt), N.ptr(xr), N.ptr(up["cvec"]), up["alpha"], up["scale"], B, P, K, N.BF16, N.stream()):
         return None
     _link_mark(up, gb)
@@ -584,23 +562,17 @@ def _head_dgrad_actbwd(g3, wt, resid, xa, up):
     Ka = wt.shape[1]
     if not _HEAD_ACTBWD or Otot > 4 or g3.dtype != xa.dtype or wt.dtype != xa.dtype:
         return None
-    key = (B, P, Otot, Ka, _dt(xa))
-    if key not in _HEAD_ACT_BLOCKS:
-        nb = _ct.c_int64(0)
-        ok = N.try_call("dgv2_bmm_nn_small_act", None, None, None, None, B, P, Otot, Ka, None, None, 1.0, 1.0, None, None, 0,
-                        _ct.addressof(nb), _dt(xa), N.stream())
-        _HEAD_ACT_BLOCKS[key] = nb.value if ok else 0
-    nblk = _HEAD_ACT_BLOCKS[key]
-    if nblk == 0:
+    need = N.scratch_elems("dgv2_bmm_nn_small_act_scratch", B, P, Otot, Ka, _dt(xa))
+    if need == 0:
         return None
     r = None if resid is None else resid.contiguous().to(xa.dtype)
     xr = xa.contiguous()
     y = torch.empty((B, P, Ka), device=xa.device, dtype=xa.dtype)
     gb = torch.empty(Ka, device=xa.device, dtype=torch.float32)
-    scratch = torch.empty(nblk * Ka, device=xa.device, dtype=torch.float32)
+    scratch = torch.empty(need, device=xa.device, dtype=torch.float32)
     N.check(g3, wt, r, xr, up["cvec"])
     N.call("dgv2_bmm_nn_small_act", N.ptr(y), N.ptr(g3), N.ptr(wt), N.ptr(r), B, P, Otot, Ka, N.ptr(xr), N.ptr(up["cvec"]),
-           up["alpha"], up["scale"], N.ptr(gb), N.ptr(scratch), scratch.numel(), None, _dt(xa), N.stream())
+           up["alpha"], up["scale"], N.ptr(gb), N.ptr(scratch), scratch.numel(), _dt(xa), N.stream())
     _link_mark(up, gb)
     return y
 
@@ -615,14 +587,8 @@ def _head_bwd_fused(gy, cvec, wt, resid, xa, up):
     if (not (_HEAD_BWD and _HEAD_ACTBWD) or Otot > 4 or gy.dtype != torch.float32 or wt.dtype != xa.dtype
             or xa.dtype not in (torch.float32, torch.bfloat16)):
         return None
-    key = ("head_bwd", B, P, Otot, Ka, _dt(xa))
-    if key not in _HEAD_ACT_BLOCKS:
-        nb = _ct.c_int64(0)
-        ok = N.try_call("dgv2_head_bwd", None, None, None, None, None, 0, _ct.addressof(nb), None, None, None, None, None,
-                        None, 1.0, 1.0, B, P, Otot, Ka, _dt(xa), N.stream())
-        _HEAD_ACT_BLOCKS[key] = nb.value if ok else 0
-    nblk = _HEAD_ACT_BLOCKS[key]
-    if nblk == 0:
+    need = N.scratch_elems("dgv2_head_bwd_scratch", B, P, Otot, Ka, _dt(xa))
+    if need == 0:
         return None
     r = None if resid is None else resid.contiguous().to(xa.dtype)
     xr = xa.contiguous()
@@ -630,9 +596,9 @@ def _head_bwd_fused(gy, cvec, wt, resid, xa, up):
     gwb = torch.empty((B, Otot, Ka), device=xa.device, dtype=torch.float32)
     gbh = torch.empty(Otot, device=xa.device, dtype=torch.float32)
     gb_up = torch.empty(Ka, device=xa.device, dtype=torch.float32)
-    scratch = torch.empty(nblk * (Ka + Otot * Ka + Otot), device=xa.device, dtype=torch.float32)
+    scratch = torch.empty(need, device=xa.device, dtype=torch.float32)
     N.check(gy, cvec, wt, r, xr, up["cvec"])
-    if not N.try_call("dgv2_head_bwd", N.ptr(y), N.ptr(gwb), N.ptr(gbh), N.ptr(gb_up), N.ptr(scratch), scratch.numel(), None,
+    if not N.try_call("dgv2_head_bwd", N.ptr(y), N.ptr(gwb), N.ptr(gbh), N.ptr(gb_up), N.ptr(scratch), scratch.numel(),
                       N.ptr(gy), N.ptr(cvec), N.ptr(wt), N.ptr(r), N.ptr(xr), N.ptr(up["cvec"]), up["alpha"], up["scale"],
                       B, P, Otot, Ka, _dt(xa), N.stream()):
         return None

@@ -9,8 +9,6 @@ pass, then one block that folds the blocks' partial sums in a fixed order and di
 reads the upstream gradient and the mask's sum on the device.  Nothing here synchronises or reads a value on the host.
 First order only.
 """
-import ctypes as _ct
-
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -82,12 +80,10 @@ class _SegMaskedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logit, label, mask, alpha, gamma, conf, want_pred):
         B, C, H, W = logit.shape
-        need = _ct.c_int64(0)
-        N.call("dgv2_seg_loss_scratch", _ct.addressof(need), B, H, W)
-        scratch = torch.empty(need.value, device=logit.device, dtype=torch.float32)
+        scratch = torch.empty(N.scratch_elems("dgv2_seg_loss_scratch", B, H, W), device=logit.device, dtype=torch.float32)
         sums = torch.empty(3, device=logit.device, dtype=torch.float32)
         pred = torch.empty((B, H, W), device=logit.device, dtype=torch.int64) if want_pred else None
-        N.call("dgv2_seg_loss_forward", None, N.ptr(pred), N.ptr(conf), N.ptr(sums), N.ptr(scratch), need.value,
+        N.call("dgv2_seg_loss_forward", None, N.ptr(pred), N.ptr(conf), N.ptr(sums), N.ptr(scratch), scratch.numel(),
                N.ptr(logit), N.ptr(label), N.ptr(mask), N.ptr(alpha), B, C, H, W, gamma, _DTYPE_CODES[logit.dtype],
                N.stream())
         ctx.save_for_backward(logit, label, mask, alpha, sums)

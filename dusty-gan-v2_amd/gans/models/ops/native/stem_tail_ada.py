@@ -51,12 +51,7 @@ class _Stem(Function):
         if gy is None:   # (only the skip branch reached the loss: not a case of the training path)
             gy = torch.zeros_like(y)
         gy = gy.contiguous().to(y.dtype)
-        key = (B, H, W_, O)
-        if key not in _STEM_SCRATCH:
-            n = _ct.c_int64(0)
-            N.call("dgv2_stem_bwd_scratch", _ct.addressof(n), B, H, W_, O)
-            _STEM_SCRATCH[key] = n.value
-        scratch = torch.empty(_STEM_SCRATCH[key], device=gy.device, dtype=torch.float32)
+        scratch = torch.empty(N.scratch_elems("dgv2_stem_bwd_scratch", B, H, W_, O), device=gy.device, dtype=torch.float32)
         gw = torch.empty((O, 2), device=gy.device, dtype=torch.float32)
         gb = torch.empty(O, device=gy.device, dtype=torch.float32)
         gx = torch.empty((B, H * W_), device=gy.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
@@ -70,9 +65,6 @@ class _Stem(Function):
         N.call("dgv2_stem_bwd_skip", N.ptr(gx), N.ptr(gw), N.ptr(gb), N.ptr(scratch), scratch.numel(), N.ptr(gy), N.ptr(y),
                N.ptr(x3), N.ptr(w32), N.ptr(gsk), *tabs, Hs, Ws, B, H, W_, O, int(ring), alpha, scale, _dt(y), N.stream())
         return (None if gx is None else gx.reshape(xshape)), gw.reshape(wshape), gb, None, None, None, None, None
-
-
-_STEM_SCRATCH = {}
 
 
 def _stem_hw(x):

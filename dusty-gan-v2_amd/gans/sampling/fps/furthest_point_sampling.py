@@ -4,11 +4,9 @@ Mirror of the reference's gans/sampling/fps/furthest_point_sampling.py:22-108 --
 error behaviour (float32, contiguous, device tensors; a CPU tensor raises like the reference's "CPU not supported") --
 over the C ABI of include/dgv2.h instead of a JIT-compiled CUDA extension.  There is no CPU fallback.
 """
-import ctypes
-
 import torch
 
-from dgv2_native import call, check, ptr, stream
+from dgv2_native import call, check, ptr, scratch_elems, stream
 
 __all__ = ["furthest_point_sampling", "gather_operation", "downsample_point_clouds", "FurthestPointSampling",
            "GatherOperation"]
@@ -30,9 +28,8 @@ class FurthestPointSampling(torch.autograd.Function):
             raise RuntimeError(f"expected (B,N,3), but got {tuple(xyz.shape)}")
         B, N, _ = xyz.shape
         out = torch.zeros(B, int(npoint), dtype=torch.int32, device=xyz.device)
-        need = ctypes.c_int64(0)
-        call("dgv2_fps_scratch", ctypes.addressof(need), B, N)
-        temp = torch.empty(need.value, dtype=torch.float32, device=xyz.device) if need.value else None
+        need = scratch_elems("dgv2_fps_scratch", B, N)
+        temp = torch.empty(need, dtype=torch.float32, device=xyz.device) if need else None
         call("dgv2_fps", ptr(out), ptr(temp), ptr(xyz), B, N, int(npoint), stream())
         ctx.mark_non_differentiable(out)
         return out

@@ -44,6 +44,17 @@ extern "C" {
 /* Library/ABI version; bumped when a signature changes. */
 int dgv2_abi_version(void);
 
+/* Workspaces.  Where the library sizes a kernel's workspace, the kernel entry <entry> has ONE host-only sibling
+ * <entry>_scratch(int64_t* elems, ...) (named without the entry's variant suffix: _ld, _pl, _skip, _forward).  It takes
+ * the geometry / dtype arguments of <entry> the size depends on, in that entry's order, launches nothing, and writes the
+ * fp32 ELEMENTS of the whole workspace (an entry that counts another unit says so).  It returns DGV2_ENOTSUP where
+ * <entry> refuses that geometry -- "use the documented fallback" -- and DGV2_EINVAL for bad arguments; a sibling sees
+ * only its own arguments, so <entry> may still refuse what depends on the others.  <entry> takes the buffer as
+ * `scratch, scratch_elems` and returns DGV2_EINVAL when it is too small.  Both call one plan function, so each size is
+ * written once.  Below, "scratch: <entry>_scratch elements" means this.
+ * (Capacities the CALLER chooses -- splits of dgv2_gemm_x3, the sumsq_cap partial buffers, the rows of
+ * dgv2_bias_act_bwd_rs -- are not workspaces in this sense.) */
+
 /* ---------------------------------------------------------------------------
  * fused bias + activation
  * replaces: fused.fused_bias_act(input, bias, refer, act, grad, alpha, scale)
@@ -138,36 +149,37 @@ int dgv2_resample_tab_add_affine(void* y, const void* x, const void* resid, cons
 /* Resampling (normally the ADJOINT tables of a blur/down) followed by the backward of a fused bias + leaky-ReLU in the
  * same pass:  y = R(x) * (ref > 0 ? 1 : alpha) * scale,  gb[c] = sum of the stored y over everything but the channel.
  * ref = forward OUTPUT of the activation, [B, out_h, out_w, C] contiguous like y; gb fp32 [C].
- * scratch fp32 [>= *blocks_needed * C]; a call with scratch == NULL only reports *blocks_needed.  DGV2_ENOTSUP when
- * the streaming kernel does not cover the geometry (then: dgv2_resample_tab_sq + dgv2_bias_act_bwd_rs).
+ * scratch: dgv2_resample_tab_actbwd_scratch elements.  DGV2_ENOTSUP when the streaming kernel does not cover the
+ * geometry (then: dgv2_resample_tab_sq + dgv2_bias_act_bwd_rs).
  * replaces: Resample adjoint (common.py:105-135) + FusedLeakyReLUFunctionBackward (fused_act.py:22-45) of the
  * discriminator's conv1 -> activation -> blur/down chain (dusty_v2.py:325-345) run backwards. */
-int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, int64_t* blocks_needed,
-                             const void* x, const void* ref, const int* idx_h, const float* coef_h,
-                             const int* cnt_h, int Eh, const int* idx_w, const float* coef_w, const int* cnt_w,
-                             int Ew, int B, int C, int in_h, int in_w, int out_h, int out_w, float alpha,
-                             float scale, int dtype, void* stream);
+int dgv2_resample_tab_actbwd_scratch(int64_t* elems, int B, int C, int out_h, int out_w, int Eh, int dtype);
+int dgv2_resample_tab_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, const void* x, const void* ref,
+                             const int* idx_h, const float* coef_h, const int* cnt_h, int Eh, const int* idx_w,
+                             const float* coef_w, const int* cnt_w, int Ew, int B, int C, int in_h, int in_w, int out_h,
+                             int out_w, float alpha, float scale, int dtype, void* stream);
 
 /* Same-size separable FIR (the blur in front of the discriminator's stride-2 convs, and its adjoint) on the MFMA cores,
  * bf16, x / y [B,H,W,C] contiguous:  y = R x.  Each pass is one 16x16x32 MFMA per 16 outputs x 16 channels with the
  * filter band as a constant operand (fir_mfma.hip).
  * dgv2_fir_same_mfma_prep builds the band operands ONCE from sparse-row tables exactly as dgv2_resample_tab_sq takes them
- *   (bands: device buffer of >= *bytes_needed bytes, 16-byte aligned; bands == NULL only reports *bytes_needed).
+ *   (bands: device buffer, 16-byte aligned, of dgv2_fir_same_mfma_prep_scratch BYTES -- not fp32 elements).
  *   Contract on the tables (a violation raises DGV2_STATUS_FIR_TABLE in *status and the bands are unusable):
  *   |idx_h[ho][a] - ho| <= 4,  (idx_w[wo][e] - wo + 8) mod W < 24,  every coefficient -- and every sum of the
  *   coefficients of one row that name the same input -- exactly representable in bf16.  DGV2_ENOTSUP unless
  *   H % 8 == 0 and W % 32 == 0.
  * dgv2_fir_same_mfma / _actbwd: DGV2_ENOTSUP unless C % 32 == 0, H % 8 == 0, W % 32 == 0 (then: dgv2_resample_tab_sq /
- *   dgv2_resample_tab_actbwd, whose contracts they share: same scratch protocol for the bias gradient).
+ *   dgv2_resample_tab_actbwd, whose contracts they share).  scratch: dgv2_fir_same_mfma_actbwd_scratch elements.
  * replaces: Blur / Resample(up = down = 1) (gans/models/ops/common.py:105-135) at gans/models/dusty_v2.py:325-345, its
  *   adjoint, and FusedLeakyReLUFunctionBackward (gans/models/ops/fused_act/fused_act.py:22-45) behind it. */
-int dgv2_fir_same_mfma_prep(void* bands, int64_t bands_bytes, int64_t* bytes_needed, const int* idx_h, const float* coef_h,
-                            const int* cnt_h, int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew,
-                            int H, int W, int* status, void* stream);
+int dgv2_fir_same_mfma_prep_scratch(int64_t* bytes, int H, int W);
+int dgv2_fir_same_mfma_prep(void* bands, int64_t bands_bytes, const int* idx_h, const float* coef_h, const int* cnt_h,
+                            int Eh, const int* idx_w, const float* coef_w, const int* cnt_w, int Ew, int H, int W,
+                            int* status, void* stream);
 int dgv2_fir_same_mfma(void* y, const void* x, const void* bands, int B, int C, int H, int W, void* stream);
-int dgv2_fir_same_mfma_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, int64_t* blocks_needed,
-                              const void* x, const void* ref, const void* bands, int B, int C, int H, int W, float alpha,
-                              float scale, void* stream);
+int dgv2_fir_same_mfma_actbwd_scratch(int64_t* elems, int B, int C, int H, int W);
+int dgv2_fir_same_mfma_actbwd(void* y, float* gb, float* scratch, int64_t scratch_elems, const void* x, const void* ref,
+                              const void* bands, int B, int C, int H, int W, float alpha, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Fourier features (positional encoding of the laser angles)
@@ -298,10 +310,11 @@ int dgv2_bmm_nn_small(void* y, const void* x, const void* w, const void* resid, 
  * [B,P,K] is this operator's forward input (the heads read the trunk's last activation):
  *   y = (x.w^T + resid) * (ref > 0 ? 1 : alpha) * ascale * row_scale[k];  gb[k] = column sums of the value before
  *   row_scale (fp32 [K]) -- FusedLeakyReLUFunctionBackward (fused_act.py:22-45) without its own pass.
- * scratch fp32 [>= *blocks_needed * K]; y == NULL with blocks_needed != NULL only reports the block count. */
+ * scratch (with ref): dgv2_bmm_nn_small_act_scratch elements. */
+int dgv2_bmm_nn_small_act_scratch(int64_t* elems, int B, int P, int O, int K, int dtype);
 int dgv2_bmm_nn_small_act(void* y, const void* x, const void* w, const void* resid, int B, int P, int O, int K,
                           const void* ref, const float* row_scale, float alpha, float ascale, float* gb,
-                          float* scratch, int64_t scratch_elems, int64_t* blocks_needed, int dtype, void* stream);
+                          float* scratch, int64_t scratch_elems, int dtype, void* stream);
 /* The whole backward of a level's output heads in ONE streaming pass + one reduce launch (round 5): the heads' input
  * x = ref [B,P,K] is read once (operand of the head weight gradient AND reference of the upstream layer's activation
  * backward), the skip gradient gyf fp32 [B,P,O] once:
@@ -310,11 +323,11 @@ int dgv2_bmm_nn_small_act(void* y, const void* x, const void* w, const void* res
  * replaces: the autograd of the two ModConv2d heads of a SynthesisBlock (gans/models/dusty_v2.py:30-57,171-178 on
  *   gans/models/ops/style.py:105-118) and of the FusedLeakyReLU in front of them (fused_act.py:22-45) -- five launches per
  *   level here before (column sum, scale + cast, dgv2_bmm_nn_small_act, dgv2_bmm_tn_small, reducers / zero fills).
- * scratch: fp32 [>= *blocks_needed * (K + O*K + O)]; y == NULL with blocks_needed: query.  DGV2_ENOTSUP as _small_act. */
-int dgv2_head_bwd(void* y, float* gw, float* gbh, float* gb_up, float* scratch, int64_t scratch_elems,
-                  int64_t* blocks_needed, const float* gyf, const float* cvec, const void* w, const void* resid,
-                  const void* ref, const float* row_scale, float alpha, float ascale, int B, int P, int O, int K, int dtype,
-                  void* stream);
+ * scratch: dgv2_head_bwd_scratch elements.  DGV2_ENOTSUP as _small_act. */
+int dgv2_head_bwd_scratch(int64_t* elems, int B, int P, int O, int K, int dtype);
+int dgv2_head_bwd(void* y, float* gw, float* gbh, float* gb_up, float* scratch, int64_t scratch_elems, const float* gyf,
+                  const float* cvec, const void* w, const void* resid, const void* ref, const float* row_scale, float alpha,
+                  float ascale, int B, int P, int O, int K, int dtype, void* stream);
 
 /* The same contraction as dgv2_bmm_nn_cat_sq, organised for the two top pyramid levels where it dominates
  * the generator ((Ka, Ks, O) = (64, 512, 32) and, as two 32-channel slabs, (128, 512, 64); bf16): a block owns a tile of pixels and walks the
@@ -346,11 +359,12 @@ int dgv2_modconv_pe_fwd_head(void* y, const void* xa, const void* xs, const void
  *   gpre[b,p,k] = bf16(t * up_scale[k]),   gb[k] = sum_{b,p} bf16(t)
  * -- bit for bit what dgv2_modconv_pe_fwd_sq (Ks = 0) followed by dgv2_bias_act_bwd_rs produce.
  * gy [B,P,K], wt [B,K,K], yref [B,P,K] (the upstream layer's forward output), gpre [B,P,K]: bf16; up_scale, gb fp32 [K];
- * scratch fp32 [scratch_elems] >= *rows_needed * K.  scratch == NULL: only *rows_needed is written, nothing is launched.
+ * scratch: dgv2_modconv_pe_dgrad_actbwd_scratch elements.
  * K in {32, 64} (generator levels 4 / 3), dtype DGV2_BF16; DGV2_ENOTSUP otherwise. */
-int dgv2_modconv_pe_dgrad_actbwd(void* gpre, float* gb, float* scratch, int64_t scratch_elems, int64_t* rows_needed,
-                                 const void* gy, const void* wt, const void* yref, const float* up_scale, float alpha,
-                                 float scale, int B, int P, int K, int dtype, void* stream);
+int dgv2_modconv_pe_dgrad_actbwd_scratch(int64_t* elems, int B, int P, int K, int dtype);
+int dgv2_modconv_pe_dgrad_actbwd(void* gpre, float* gb, float* scratch, int64_t scratch_elems, const void* gy,
+                                 const void* wt, const void* yref, const float* up_scale, float alpha, float scale, int B,
+                                 int P, int K, int dtype, void* stream);
 
 /* Per-sample weights of the modulated conv, written directly as the GEMM operand, and the exact
  * backward of that preparation (max-normalisations, modulation, demodulation, input-magnitude

@@ -1937,17 +1937,15 @@ def test_fir_same_size_with_activation_backward_on_mfma(nat):
 def test_fir_mfma_flags_tables_outside_its_windows(nat):
     """The table contract is checked on the device when the band operands are built: a decimating table handed to the
     same-size prep raises the flag, a blur's does not."""
-    import ctypes
     import dgv2_native as N
 
     def prep(spec, Hin, Win, H, W):
         (ih, chh, nh, Eh), (iw, cw, nw, Ew) = spec.tables(Hin, Win, False, DEV)
-        need = ctypes.c_int64(0)
         tabs = (N.ptr(ih), N.ptr(chh), N.ptr(nh), Eh, N.ptr(iw), N.ptr(cw), N.ptr(nw), Ew, H, W, N.ptr(N.status_word()))
-        N.call("dgv2_fir_same_mfma_prep", None, 0, ctypes.addressof(need), *tabs, N.stream())
-        assert need.value in (1024 * (H // 8 + 1 + W // 16), 1024 * (H // 4 + 1 + W // 16))
-        buf = torch.empty(need.value, device=DEV, dtype=torch.uint8)
-        N.call("dgv2_fir_same_mfma_prep", N.ptr(buf), buf.numel(), None, *tabs, N.stream())
+        need = N.scratch_elems("dgv2_fir_same_mfma_prep_scratch", H, W)
+        assert need in (1024 * (H // 8 + 1 + W // 16), 1024 * (H // 4 + 1 + W // 16))
+        buf = torch.empty(need, device=DEV, dtype=torch.uint8)
+        N.call("dgv2_fir_same_mfma_prep", N.ptr(buf), buf.numel(), *tabs, N.stream())
         return N.status_read()
 
     assert prep(nat.ResampleSpec([1, 3, 3, 1]), 32, 64, 32, 64) == 0
