@@ -487,7 +487,7 @@ int dgv2_conv8_try(void* y, int ldy, const void* x, const void* w, int B, int Hi
 
 // The forward 3x3 ring conv (stride 1 or 2, pad 1) on the weight IMAGE of dgv2_conv_weight_bank_ex:
 //   y [B, Hin / stride, Win / stride, O] (bf16) = act( conv(x [B, Hin, Win, Cin], w) + resid + bias ) * scale.
-// DGV2_ENOTSUP where the eight-wave engine does not cover the geometry (callers then run dgv2_conv_taps on the
+// DGV2_ENOTSUP where the eight-wave engine does not cover the geometry (callers then run dgv2_conv_direct_fwd on the
 // row-layout weights).
 extern "C" int dgv2_conv3x3_fwd8(void* y, const void* x, const void* w8, int B, int Hin, int Win, int Cin, int O,
                                  int stride, const float* bias, const void* resid, int act, float alpha, float scale,
@@ -506,7 +506,7 @@ extern "C" int dgv2_conv3x3_fwd8(void* y, const void* x, const void* w8, int B, 
 // The stride-1 data gradient of the same 3x3 ring conv on the TRANSPOSED staging image (w8t of dgv2_conv_weight_bank_ex):
 //   gx [B, H, W, C] (bf16) = sum_{ky,kx,o} gy[B, Hz(h + 1 - ky), wrap(w + 1 - kx), o] * w[o, ky, kx, c]
 //                            + the replicate-row terms of rows 0 and H - 1  (+ resid: the gradient of a sibling branch).
-// DGV2_ENOTSUP where the engine does not cover the geometry (callers then run dgv2_conv_taps_ex on wt).
+// DGV2_ENOTSUP where the engine does not cover the geometry (callers then run dgv2_conv_direct_dgrad on wt).
 extern "C" int dgv2_conv3x3_dgrad8(void* gx, const void* gy, const void* w8t, int B, int H, int W, int C, int O,
                                    const void* resid, int dtype, void* stream) {
   if (!gx || !gy || !w8t || B < 1 || H < 1 || W < 1 || C < 1 || O < 1) return DGV2_EINVAL;

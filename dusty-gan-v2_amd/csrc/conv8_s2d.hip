@@ -6,7 +6,7 @@
 //   ResidualBlock.conv2 (3x3, stride 2, behind the blur), gans/models/dusty_v2.py:337-345.
 //
 //   gx[b, 2i + py, 2j + px, c] = sum_{(dy, ky) in T(py)} sum_{(dx, kx) in T(px)} sum_o gy[b, i + dy, wrap(j + dx), o] wt[c, ky*3 + kx, o]
-//   T(0) = {(0, 1)}, T(1) = {(1, 0), (0, 2)}   (conv.py:_axis_taps_s2; gy rows past the last one are zero),
+//   T(0) = {(0, 1)}, T(1) = {(1, 0), (0, 2)}   (conv_direct.hip: dgrad_s2_class_form; gy rows past the last one are zero),
 //   + the replicate row of the forward padding: output row 0 sees gy row 0 once more through the ky = 0 weights.
 //
 // Two forms.  FOUR-ROW TILES, ALL FOUR CLASSES IN ONE LAUNCH (PY = 2: 128 accumulator registers fit; the border row's terms
@@ -282,7 +282,7 @@ int launch_s2d(void* gx, const void* gy, const void* wt, S2D p, hipStream_t st) 
 // The stride-2 data gradient of the 3x3 ring conv (pad 1) on the transposed row weights wt [C, 9, O] (the weight bank's wt):
 //   gx [B, 2 Hg, 2 Wg, C] (bf16) from gy [B, Hg, Wg, O], the replicate row of output row 0 included; two launches (output row
 //   parities).  DGV2_ENOTSUP where the engine does not cover the geometry (C % 128, O % 32, O >= 64, Hg % 4, Wg % 32, bf16):
-//   callers then run dgv2_conv_taps_ex.
+//   callers then run dgv2_conv_direct_dgrad.
 extern "C" int dgv2_conv3x3_s2_dgrad8(void* gx, const void* gy, const void* wt, int B, int Hg, int Wg, int C, int O, int dtype,
                                       void* stream) {
   if (!gx || !gy || !wt || B < 1 || Hg < 1 || Wg < 1 || C < 1 || O < 1) return DGV2_EINVAL;

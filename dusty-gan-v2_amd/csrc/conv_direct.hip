@@ -1,4 +1,4 @@
-// Direct (LDS halo-tile) convolution on the MFMA cores, channels-last, with a generic TAP LIST.
+// Direct (LDS halo-tile) convolution on the MFMA cores, channels-last: dgv2_conv_direct_fwd / _fwd_fp8 / _dgrad.
 //
 // One engine covers every dense conv of the discriminator and their data gradients
 // (reference: ops.Conv2d in gans/models/ops/common.py:187-210 at gans/models/dusty_v2.py:325-385,
@@ -62,7 +62,7 @@ struct DConv {
 #else
 #define CP_ABL 0
 #endif
-  int s2d;          // four classes = the canonical stride-2 3x3 data gradient (host-checked tap list): unrolled taps
+  int s2d;          // four classes = the stride-2 3x3 data gradient (dgrad_s2_form): unrolled taps
   int wres;         // tap-list kernels, 2 K-chunks: both chunks' weight slabs stay in LDS for the block's whole walk
   int nt;           // streaming output stores (outputs >= DGV2_NT_MIN_MB that no residual read revisits)
   // XCD-aware block order (1-D launch): workgroup n runs on XCD n % 8 (each XCD has its own L2), so the gz blocks that
@@ -79,7 +79,7 @@ struct DConv {
   // border extras: tap (x_dy, x_dx, weight slot x_slot) added to class x_cls for output row x_row only
   // (the replicate-padding rows of the data gradient, formerly separate one-row accumulate launches)
   int nx, x_dy[6], x_dx[6], x_slot[6], x_cls[6], x_row[6];
-  // The six extras are exactly the replicate-row terms of the stride-1 3x3 data gradient (host-checked: border_ok).
+  // The six extras are exactly the replicate-row terms of the stride-1 3x3 data gradient (border_extras; border_ok: and the switches allow it).
   // The unrolled-tap data-gradient instances (F33 = 2) then run WITHOUT extras (border = 1, nx = 0): the term of a dead
   // tap (dy = -1 at output row 0, dy = +1 at the last row) is the border row itself through the weights of the tap
   // mirrored in dy, so it is issued next to THAT tap's MFMAs (weights in registers, one more pixel-fragment read: tap
@@ -845,10 +845,11 @@ int launch_pipe(void* y, const void* x, const void* w, DConv p, hipStream_t st) 
 
 }  // namespace
 
-// conv_strip.hip: streaming kernel for 3x3 stride-1 ring convs with 32 -> 32 channels (bf16); -2 = not covered
-int dgv2_conv_strip_try(void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int ntaps, int wtaps,
-                        const int* taps4, int nextra, const int* extras5, int hzero, const float* bias,
-                        const void* resid, int act, float alpha, float scale, hipStream_t st);
+// conv_strip.hip: streaming kernel for 3x3 stride-1 ring convs with 32 -> 32 channels (bf16); tap (dy, dx) reads weight
+// slot widx0 + ((dy + 1) * 3 + dx + 1) * wstep, border: the replicate-row terms of the data gradient; -2 = not covered
+int dgv2_conv_strip_try(void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int wtaps, int widx0,
+                        int wstep, int border, int hzero, const float* bias, const void* resid, int act, float alpha,
+                        float scale, hipStream_t st);
 
 // conv8.hip: eight-wave form of the unrolled 3x3 forward conv (two groups of four waves sharing the halo tile or the
 // weight slab); -2 = not covered
@@ -885,208 +886,192 @@ int dispatch_pipe(void* y, const void* x, const void* w, const DConv& p, bool f3
   return launch_pipe<T, TY, TO, 1, 10, 1>(y, x, w, p, st);
 }
 
-}  // namespace
-
-extern "C" int dgv2_conv_taps_ld(void* y, int ldy, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg,
-                                 int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w,
-                                 int out_stride, int ncls, const int* cls_host, int ntaps, int wtaps,
-                                 const int* taps_host, int nextra, const int* extras_host, int hzero, int ring,
-                                 int accumulate, const float* bias, const void* resid, int act, float alpha,
-                                 float scale, int dtype, void* stream);
-
-// y[b, gh*out_stride+ooff_h(c), gw*out_stride+ooff_w(c), o] (=|+=) act( sum_{t in class c} sum_ch
-//     x[b, H(gh*in_stride+ioff_h+dy_t), W(gw*in_stride+ioff_w+dx_t), ch] * w[o, widx_t, ch] + resid + bias[o] )
-// for gh < Hg, gw < Wg and every output class c.  taps_host: HOST pointer to ntaps quadruples
-// (dy, dx, widx, cls), sorted by class, ntaps <= 9; cls_host: ncls pairs (ooff_h, ooff_w), ncls in {1, 4};
-// extras_host: nextra <= 6 quintuples (dy, dx, widx, cls, row): an additional tap for output row gh == row only,
-// widx must be one of the main taps' (its weights are already staged).
-// H(): clamp (hzero = 0) or zero outside [0,Hin) (hzero = 1); W(): wrap (ring) or clamp.
-// Cin must be a multiple of 32 (bf16) / 16 (fp32).  Classes / extras need the pipelined kernel; geometries it
-// does not cover return DGV2_ENOTSUP (callers then issue one launch per class / border row).
-extern "C" int dgv2_conv_taps_ex(void* y, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg,
-                                 int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w,
-                                 int out_stride, int ncls, const int* cls_host, int ntaps, int wtaps,
-                                 const int* taps_host, int nextra, const int* extras_host, int hzero, int ring,
-                                 int accumulate, const float* bias, const void* resid, int act, float alpha,
-                                 float scale, int dtype, void* stream) {
-  return dgv2_conv_taps_ld(y, O, x, w, B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy, in_stride, ioff_h, ioff_w, out_stride, ncls,
-                           cls_host, ntaps, wtaps, taps_host, nextra, extras_host, hzero, ring, accumulate, bias, resid, act,
-                           alpha, scale, dtype, stream);
-}
-
-// dgv2_conv_taps_ex writing the O output channels into rows of ldy >= O channels (y / resid point at the first of them):
-// a launch may then produce a channel RANGE of a wider tensor -- the 528-channel data gradient of the discriminator's
-// epilogue conv runs as 512 + 16 channels instead of nine 64-channel slabs of which the last is three quarters empty.
-static int conv_taps_impl(void* y, int ldy, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg,
-                          int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w,
-                          int out_stride, int ncls, const int* cls_host, int ntaps, int wtaps,
-                          const int* taps_host, int nextra, const int* extras_host, int hzero, int ring,
-                          int accumulate, const float* bias, const void* resid, int act, float alpha,
-                          float scale, int dtype, const float* acc_scale, void* stream) {
-  if (!y || !x || !w || !taps_host || !cls_host || ntaps < 1 || ntaps > 9 || wtaps < 1 || ldy < O) return DGV2_EINVAL;
-  if (ldy != O && (ldy % (dtype == DGV2_F32 ? 4 : 8))) return DGV2_EINVAL;   // 16-byte stores stay aligned
-  if (ncls != 1 && ncls != 4) return DGV2_EINVAL;
-  if (nextra < 0 || nextra > 6 || (nextra > 0 && !extras_host)) return DGV2_EINVAL;
-  if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Hg <= 0 || Wg <= 0 || O <= 0 || in_stride < 1 || out_stride < 1)
-    return DGV2_EINVAL;
-  if (act != 0 && act != 3) return DGV2_EINVAL;
-  const int kstep = dtype == DGV2_FP8 ? 64 : (dtype == DGV2_BF16 ? 32 : 16);   // one 64-byte K-chunk
-  if (Cin % kstep || !aligned16(x) || !aligned16(w)) return DGV2_EINVAL;
-  DConv p;
-  p.acc_scale = acc_scale;
-  p.nt = 0;
-  p.hper = 0; p.hrows = 0;
-  p.B = B; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Hg = Hg; p.Wg = Wg; p.O = O; p.Hy = Hy; p.Wy = Wy; p.ldy = ldy;
-  p.in_stride = in_stride; p.ioff_h = ioff_h; p.ioff_w = ioff_w;
-  p.out_stride = out_stride; p.ooff_h = cls_host[0]; p.ooff_w = cls_host[1];
-  p.ntaps = ntaps; p.wtaps = wtaps;
-  p.ncls = ncls;
-  for (int c = 0; c < 4; ++c) {
-    p.cls_ooh[c] = c < ncls ? cls_host[2 * c] : 0;
-    p.cls_oow[c] = c < ncls ? cls_host[2 * c + 1] : 0;
-  }
-  // single-class launches: taps in (dy, dx) order (the sum does not depend on it; the full 3x3 grid then is tap
-  // t = (dy - dymin) * 3 + (dx - dxmin), which the unrolled kernel variant relies on)
-  int sorted[36];
-  if (ncls == 1) {
-    for (int t = 0; t < 4 * ntaps; ++t) sorted[t] = taps_host[t];
-    for (int i = 1; i < ntaps; ++i)
-      for (int j = i; j > 0 && (sorted[4 * j] < sorted[4 * j - 4] ||
-                                (sorted[4 * j] == sorted[4 * j - 4] && sorted[4 * j + 1] < sorted[4 * j - 3])); --j)
-        for (int k = 0; k < 4; ++k) { const int v = sorted[4 * j + k]; sorted[4 * j + k] = sorted[4 * j - 4 + k]; sorted[4 * j - 4 + k] = v; }
-    taps_host = sorted;
-  }
-  int dymin = 1 << 30, dymax = -(1 << 30), dxmin = 1 << 30, dxmax = -(1 << 30);
-  int prev_cls = 0;
-  for (int c = 0; c < 5; ++c) p.cls_t0[c] = ntaps;
-  p.cls_t0[0] = 0;
-  for (int t = 0; t < 9; ++t) {
-    p.dy[t] = p.dx[t] = p.widx[t] = 0;
-    if (t < ntaps) {
-      p.dy[t] = taps_host[4 * t]; p.dx[t] = taps_host[4 * t + 1]; p.widx[t] = taps_host[4 * t + 2];
-      const int c = taps_host[4 * t + 3];
-      if (p.widx[t] < 0 || p.widx[t] >= wtaps || c < prev_cls || c >= ncls) return DGV2_EINVAL;
-      for (int k = prev_cls + 1; k <= c; ++k) p.cls_t0[k] = t;
-      prev_cls = c;
-      dymin = p.dy[t] < dymin ? p.dy[t] : dymin; dymax = p.dy[t] > dymax ? p.dy[t] : dymax;
-      dxmin = p.dx[t] < dxmin ? p.dx[t] : dxmin; dxmax = p.dx[t] > dxmax ? p.dx[t] : dxmax;
-    }
-  }
-  p.nx = nextra;
-  for (int e = 0; e < 6; ++e) {
-    p.x_dy[e] = p.x_dx[e] = p.x_slot[e] = p.x_cls[e] = 0;
-    p.x_row[e] = -1;
-    if (e < nextra) {
-      const int* q = extras_host + 5 * e;
-      p.x_dy[e] = q[0]; p.x_dx[e] = q[1]; p.x_cls[e] = q[3]; p.x_row[e] = q[4];
-      int slot = -1;
-      for (int t = 0; t < ntaps; ++t)
-        if (p.widx[t] == q[2]) slot = t;
-      if (slot < 0 || q[3] < 0 || q[3] >= ncls) return DGV2_EINVAL;
-      p.x_slot[e] = slot;
-      dymin = q[0] < dymin ? q[0] : dymin; dymax = q[0] > dymax ? q[0] : dymax;
-      dxmin = q[1] < dxmin ? q[1] : dxmin; dxmax = q[1] > dxmax ? q[1] : dxmax;
-    }
-  }
-  p.dymin = dymin; p.dxmin = dxmin;
-  p.rows = dymax - dymin + 1;   // tap extents; the launchers add the tile extent
-  p.cols = dxmax - dxmin + 1;
-  p.hzero = hzero; p.ring = ring; p.accumulate = accumulate;
-  p.tpb = 1; p.inv_cols = 0.f; p.wres = 0; p.s2d = 0; p.xcd = 0; p.gx = p.gy = p.gz = 1;
+// ---------------------------------------------------------------------------------------------
+// The forms.  The caller states a conv (dgv2_conv_direct_fwd / _fwd_fp8 / _dgrad); a builder fills the DConv of its form:
+//   forward k x k, stride 1 | 2          box_taps over (ky - pad, kx - pad), slots ky * k + kx, rows clamp
+//   data gradient 1 x 1                  one tap on gy with the transposed weights, rows zero-filled (hzero)
+//   data gradient 3 x 3, stride 1        box_taps over (1 - ky, 1 - kx), slots 8 - t; + border_extras: one launch
+//   data gradient 3 x 3, stride 2        s2_classes: four parity classes + the top-border extras, one launch
+//   their unfused sequences              one-row accumulate launches / one launch per class: box_taps again
+// Every y[b, gh * out_stride + ooff_h(c), gw * out_stride + ooff_w(c), o] (=|+=) act( sum_{t in class c} sum_ch
+//     x[b, H(gh * in_stride + ioff_h + dy_t), W(gw * in_stride + ioff_w + dx_t), ch] * w[o, widx_t, ch] + resid + bias[o] ),
+// H(): clamp or zero outside [0, Hin) (hzero), W(): ring wrap.
+// ---------------------------------------------------------------------------------------------
+DConv form_base(int B, int Hin, int Win, int Cin, int Hg, int Wg, int O, int Hy, int Wy, int in_stride, int out_stride,
+                int hzero) {
+  DConv p{};
+  p.B = B; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Hg = Hg; p.Wg = Wg; p.O = O; p.Hy = Hy; p.Wy = Wy; p.ldy = O;
+  p.in_stride = in_stride; p.out_stride = out_stride; p.hzero = hzero; p.ring = 1;
+  p.ncls = 1; p.tpb = 1; p.gx = p.gy = p.gz = 1;
+  for (int e = 0; e < 6; ++e) p.x_row[e] = -1;
+  p.alpha = 0.2f; p.scale = 1.f;
 #ifdef DGV2_ABLATE
   p.ablate = getenv("DGV2_CP_ABLATE") ? atoi(getenv("DGV2_CP_ABLATE")) : 0;
 #endif
-  p.bias = bias; p.resid = resid; p.ybase = y; p.act = act; p.alpha = alpha; p.scale = scale;
-  hipStream_t st = (hipStream_t)stream;
+  return p;
+}
+
+// One class over the tap box [dymin, dymin + rows) x [dxmin, dxmin + cols), written in (dy, dx) order -- tap
+// t = (dy - dymin) * cols + (dx - dxmin), which the unrolled 3x3 variants rely on --; the weight slot of tap (dy, dx) is
+// w0 + (dy - dymin) * wdy + (dx - dxmin) * wdx of w [O, wtaps, Cin].
+void box_taps(DConv& p, int dymin, int rows, int dxmin, int cols, int w0, int wdy, int wdx, int wtaps) {
+  p.dymin = dymin; p.dxmin = dxmin; p.rows = rows; p.cols = cols;   // tap extents; the launchers add the tile extent
+  p.ntaps = rows * cols; p.wtaps = wtaps;
+  for (int t = 0; t < p.ntaps; ++t) {
+    p.dy[t] = dymin + t / cols; p.dx[t] = dxmin + t % cols;
+    p.widx[t] = w0 + (t / cols) * wdy + (t % cols) * wdx;
+  }
+  for (int c = 1; c < 5; ++c) p.cls_t0[c] = p.ntaps;
+}
+
+void out_offset(DConv& p, int ooff_h, int ooff_w) {
+  p.ooff_h = p.cls_ooh[0] = ooff_h;
+  p.ooff_w = p.cls_oow[0] = ooff_w;
+}
+
+// forward: x [B,H,W,Cin], w [O,k*k,Cin] -> y [B,Ho,Wo,O]
+DConv fwd_form(int B, int H, int W, int Cin, int O, int k, int stride) {
+  const int pad = (k - 1) / 2, Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  DConv p = form_base(B, H, W, Cin, Ho, Wo, O, Ho, Wo, stride, 1, 0);
+  box_taps(p, -pad, k, -pad, k, 0, k, 1, k * k);
+  return p;
+}
+
+// data gradient, stride 1: gy [B,H,W,O], wt [C,k*k,O] -> gx [B,H,W,C].  Circular W padding transposes to a wrap of the gy
+// coordinate; tap (dy, dx) = (1 - ky, 1 - kx) reads slot ky * 3 + kx = 8 - t.
+DConv dgrad_s1_form(int B, int H, int W, int C, int O, int k) {
+  DConv p = form_base(B, H, W, O, H, W, C, H, W, 1, 1, 1);
+  if (k == 1) box_taps(p, 0, 1, 0, 1, 0, 0, 0, 1);
+  else box_taps(p, -1, 3, -1, 3, 8, -3, -1, 9);
+  return p;
+}
+
+// The replicate rows of the H padding as border extras of output rows 0 and H - 1: padded row -1 (-> h = 0) is read by
+// ky = 0 of output row 0, padded row H (-> h = H - 1) by ky = 2 of output row H - 1 -- the taps (0, dx) with the weights of
+// the taps (+1, dx) / (-1, dx), whose slabs are staged as taps 6 + j / j.
+void border_extras(DConv& p) {
+  p.nx = 6;
+  p.border_ok = 1;   // the unrolled instances may re-weight the border rows instead (DConv::border)
+  for (int e = 0; e < 6; ++e) {
+    const int kx = e % 3, top = e < 3;
+    p.x_dy[e] = 0; p.x_dx[e] = 1 - kx; p.x_cls[e] = 0;
+    p.x_slot[e] = top ? 8 - kx : 2 - kx;
+    p.x_row[e] = top ? 0 : p.Hg - 1;
+  }
+}
+
+// ... and as a one-row accumulate launch of the unfused sequence (bottom = 0: output row 0, else row H - 1)
+DConv dgrad_s1_row_form(int B, int H, int W, int C, int O, int bottom) {
+  DConv p = form_base(B, H, W, O, 1, W, C, H, W, 1, 1, 1);
+  box_taps(p, 0, 1, -1, 3, bottom ? 8 : 2, 0, -1, 9);
+  p.ioff_h = bottom ? H - 1 : 0;
+  out_offset(p, p.ioff_h, 0);
+  p.accumulate = 1;
+  return p;
+}
+
+// data gradient, stride 2 (pad 1, even H and W): gy [B,H/2,W/2,O] -> gx [B,H,W,C].  Output parity class (ph, pw) sees the gy
+// pixels (dy, dx) in {0..ph} x {0..pw} through kernel row ky = 1 (ph = 0) or 2 - 2 dy, column kx likewise.
+// One class per launch (row0: the top-border launch of class (0, pw) -- padded row -1 is read by ky = 0 of output row 0):
+DConv dgrad_s2_class_form(int B, int H, int W, int C, int O, int ph, int pw, int row0) {
+  DConv p = form_base(B, H / 2, W / 2, O, row0 ? 1 : H / 2, W / 2, C, H, W, 1, 2, 1);
+  box_taps(p, 0, ph + 1, 0, pw + 1, (ph ? 2 : (row0 ? 0 : 1)) * 3 + (pw ? 2 : 1), -6, -2, 9);
+  out_offset(p, ph, pw);
+  p.accumulate = row0;
+  return p;
+}
+
+// All four classes and the top border in one launch: the gy halo tile and the nine weight slabs are staged once.  The taps
+// stand in the order conv_pipe_kernel's unrolled s2d branch reads them (TDY / TDX / TCL there).
+DConv dgrad_s2_form(int B, int H, int W, int C, int O) {
+  DConv p = form_base(B, H / 2, W / 2, O, H / 2, W / 2, C, H, W, 1, 2, 1);
+  static const int dy9[9] = {0, 0, 0, 1, 0, 1, 1, 0, 0}, dx9[9] = {0, 1, 0, 0, 0, 1, 0, 1, 0};
+  static const int w9[9] = {4, 3, 5, 1, 7, 0, 2, 6, 8}, t0[5] = {0, 1, 3, 5, 9};
+  p.ntaps = 9; p.wtaps = 9; p.rows = p.cols = 2;
+  for (int t = 0; t < 9; ++t) { p.dy[t] = dy9[t]; p.dx[t] = dx9[t]; p.widx[t] = w9[t]; }
+  p.ncls = 4;
+  for (int c = 0; c < 5; ++c) p.cls_t0[c] = t0[c];
+  for (int c = 0; c < 4; ++c) { p.cls_ooh[c] = c >> 1; p.cls_oow[c] = c & 1; }
+  // top border: classes (0, 0) and (0, 1) at output row 0 through kernel row 0, i.e. the slabs of taps 3 / 5, 6
+  static const int xdx[3] = {0, 1, 0}, xslot[3] = {3, 5, 6}, xcls[3] = {0, 1, 1};
+  p.nx = 3;
+  for (int e = 0; e < 3; ++e) { p.x_dx[e] = xdx[e]; p.x_slot[e] = xslot[e]; p.x_cls[e] = xcls[e]; p.x_row[e] = 0; }
+  p.s2d = 1;
+  return p;
+}
+
+// the ring wrap of the pipelined kernel assumes -Win <= gw < 4*Win
+bool wrap_ok(const DConv& p) {
+  return p.ioff_w + p.dxmin >= -p.Win &&
+         p.in_stride * ((p.Wg + DTW - 1) / DTW * DTW) + p.ioff_w + p.dxmin + p.cols - 1 < 4 * p.Win;
+}
+
+// One launch of the engine for a built form.  grid33: the taps are the full 3x3 grid with slots affine in t (forward 3x3
+// and the whole stride-1 data gradient); p.border_ok / p.s2d arrive as the form's claim and are narrowed by the switches.
+// y / resid may point into a wider tensor (p.ldy >= p.O: a channel range).
+// Returns DGV2_ENOTSUP, before anything is launched, where output classes or border extras meet a geometry only the
+// synchronous kernel covers (it has neither); the bare forms always run.
+int conv_launch(DConv p, bool grid33, void* y, const void* x, const void* w, int dtype, hipStream_t st) {
+  p.ybase = y;
+  const bool plain = p.ncls == 1 && p.nx == 0;
   int rc = 0;
-  if (dtype == DGV2_BF16 && ldy == O && ncls == 1 && in_stride == 1 && out_stride == 1 && ring && !accumulate && Hin == Hg &&
-      Win == Wg && Hy == Hg && Wy == Wg && ioff_h == 0 && ioff_w == 0 && cls_host[0] == 0 && cls_host[1] == 0 &&
-      aligned16(y) && (!resid || aligned16(resid))) {
+  if (dtype == DGV2_BF16 && grid33 && p.in_stride == 1 && p.ldy == p.O && aligned16(y) && (!p.resid || aligned16(p.resid))) {
     // full-resolution 32 -> 32 channel layers: the strip-streaming kernel (conv_strip.hip)
-    rc = dgv2_conv_strip_try(y, x, w, B, Hin, Win, Cin, O, ntaps, wtaps, taps_host, nextra, extras_host, hzero, bias,
-                             resid, act, alpha, scale, st);
+    rc = dgv2_conv_strip_try(y, x, w, p.B, p.Hin, p.Win, p.Cin, p.O, p.wtaps, p.widx[0], p.widx[1] - p.widx[0], p.border_ok,
+                             p.hzero, p.bias, p.resid, p.act, p.alpha, p.scale, st);
     if (rc != -2) {
       if (rc) return rc;
       DGV2_RETURN_LAST();
     }
-    rc = 0;
   }
+  static const bool no_f33 = getenv("DGV2_NO_F33") != nullptr;   // A/B switch for benchmarking
+  const bool f33 = !no_f33 && grid33;
+  if ((dtype == DGV2_BF16 || dtype == DGV2_FP8) && f33 && !p.hzero) {
+    // forward 3x3 convs from 64 channels up: the eight-wave engine (conv8.hip) where it covers the geometry
+    rc = dgv2_conv8_try(y, p.ldy, x, w, p.B, p.Hin, p.Win, p.Cin, p.Hg, p.Wg, p.O, p.in_stride, p.wtaps, p.widx[0],
+                        p.widx[1] - p.widx[0], p.bias, p.acc_scale, p.resid, p.act, p.alpha, p.scale, dtype, st, 0, 0);
+    if (rc != -2) {
+      if (rc) return rc;
+      DGV2_RETURN_LAST();
+    }
+  }
+  const bool wrap = wrap_ok(p);
   // 4-row maps (the discriminator's last block and its epilogue): an 8-row tile over a PAIR of images stages the weight
   // slab once for both (fp32 epilogue conv forward 728 -> 632 us, bf16 121 -> 93 us at 128 x 4 x 32)
   static const bool no_pairs = getenv("DGV2_NO_PAIRS") != nullptr;   // A/B switch for benchmarking
-  if (!no_pairs && ncls == 1 && in_stride == 1 && out_stride == 1 && Hin == 4 && Hg == 4 && Hy == 4 && ioff_h == 0 &&
-      cls_host[0] == 0 && (B & 1) == 0 && O >= 64 &&
-      (int64_t)(B / 2) * ((O + 63) / 64) * ((Wg + DTW - 1) / DTW) >= 512) {   // still two blocks per CU: fewer were slower
+  if (!no_pairs && p.ncls == 1 && p.in_stride == 1 && p.out_stride == 1 && p.Hin == 4 && p.Hg == 4 && p.Hy == 4 &&
+      p.ioff_h == 0 && p.ooff_h == 0 && (p.B & 1) == 0 && p.O >= 64 &&
+      (int64_t)(p.B / 2) * ((p.O + 63) / 64) * ((p.Wg + DTW - 1) / DTW) >= 512) {   // still two blocks per CU: fewer were slower
     p.hper = 4;
-    p.B = B / 2; p.Hin = 8; p.Hg = 8; p.Hy = 8;
+    p.B /= 2; p.Hin = 8; p.Hg = 8; p.Hy = 8;
   }
-  static const bool no_pipe = getenv("DGV2_NO_PIPE") != nullptr;   // A/B switch for benchmarking
-  // the ring wrap of the pipelined kernel assumes -Win <= gw < 4*Win
-  const bool wrap_ok = !ring || (ioff_w + dxmin >= -Win && in_stride * ((Wg + DTW - 1) / DTW * DTW) + ioff_w + dxmax < 4 * Win);
-  const bool plain = ncls == 1 && nextra == 0;
-  static const bool no_f33 = getenv("DGV2_NO_F33") != nullptr;   // A/B switch for benchmarking
-  bool f33 = !no_f33 && ncls == 1 && (in_stride == 1 || (in_stride == 2 && out_stride == 1 && !hzero)) && ntaps == 9 &&
-             p.rows == 3 && p.cols == 3;
-  for (int t = 0; f33 && t < 9; ++t) f33 = p.dy[t] == dymin + t / 3 && p.dx[t] == dxmin + t % 3;
-  for (int t = 2; f33 && t < 9; ++t) f33 = p.widx[t] - p.widx[t - 1] == p.widx[1] - p.widx[0];   // weight slots affine in t
-  for (int e = 0; f33 && hzero && e < nextra; ++e)   // zero rows are not staged as zeros there: extras must read real rows
-    f33 = (unsigned)(p.x_row[e] * in_stride + ioff_h + p.x_dy[e]) < (unsigned)Hin;
-  {
-    // border_ok: the extras are the replicate-row terms of the same-size stride-1 3x3 data gradient -- at output row 0
-    // the taps (0, dx) with the weights of the taps (+1, dx), at the last row with those of (-1, dx)
-    static const bool no_border = getenv("DGV2_NO_BORDER_REWEIGHT") != nullptr;   // A/B switch for benchmarking
-    const int hrows_img = p.hper ? p.hper : p.Hg;
-    bool ok = !no_border && f33 && hzero && nextra == 6 && in_stride == 1 && out_stride == 1 && ioff_h == 0 && dymin == -1 &&
-              hrows_img >= 2 && (p.hper ? true : Hin == Hg);
-    unsigned seen = 0;
-    for (int e = 0; ok && e < 6; ++e) {
-      const int top = p.x_row[e] == 0, bot = p.x_row[e] == hrows_img - 1, j = p.x_dx[e] - dxmin;
-      ok = (top || bot) && p.x_dy[e] == 0 && p.x_cls[e] == 0 && j >= 0 && j < 3 && p.x_slot[e] == (top ? 6 + j : j);
-      seen |= 1u << ((top ? 0 : 3) + (j & 3));
-    }
-    p.border_ok = (ok && seen == 63u) ? 1 : 0;
-  }
-  if ((dtype == DGV2_BF16 || dtype == DGV2_FP8) && f33 && ncls == 1 && nextra == 0 && !accumulate && !hzero && ring &&
-      out_stride == 1 && ioff_h == 0 && ioff_w == 0 && cls_host[0] == 0 && cls_host[1] == 0 && dymin == -1 && dxmin == -1 &&
-      Hy == Hg && Wy == Wg) {
-    // forward 3x3 convs from 64 channels up: the eight-wave engine (conv8.hip) where it covers the geometry
-    rc = dgv2_conv8_try(y, ldy, x, w, B, Hin, Win, Cin, Hg, Wg, O, in_stride, wtaps, p.widx[0], p.widx[1] - p.widx[0], bias,
-                        acc_scale, resid, act, alpha, scale, dtype, st, 0, 0);
-    if (rc != -2) {
-      if (rc) return rc;
-      DGV2_RETURN_LAST();
-    }
-    rc = 0;
-  }
+  // border_ok (border_extras): the unrolled instances re-weight the border rows instead of running the extras; two rows at
+  // least, or rows 0 and H - 1 are one row
+  static const bool no_border = getenv("DGV2_NO_BORDER_REWEIGHT") != nullptr;   // A/B switch for benchmarking
+  if (no_border || !f33 || (p.hper ? p.hper : p.Hg) < 2) p.border_ok = 0;
   if (dtype == DGV2_FP8) {
-    // e4m3 operands, bf16 result / residual: the forward convs behind the FIRs (>= 64 output channels, one class)
-    if (ncls != 1 || nextra || accumulate || O < 64 || !wrap_ok) return DGV2_ENOTSUP;
+    // e4m3 operands, bf16 result / residual: the forward convs behind the FIRs (>= 64 output channels)
+    if (p.O < 64 || !wrap) return DGV2_ENOTSUP;
     rc = dispatch_pipe<fp8_t, 64, bf16_t>(y, x, w, p, f33, st);
     if (rc == -2) return DGV2_ENOTSUP;
     if (rc) return rc;
     DGV2_RETURN_LAST();
   }
   static const bool no_s2d = getenv("DGV2_NO_S2D") != nullptr;   // A/B switch for benchmarking
-  if (!no_s2d && ncls == 4 && ntaps == 9 && in_stride == 1 && out_stride == 2 && hzero && dymin == 0 && dxmin == 0 &&
-      p.rows == 2 && p.cols == 2) {
-    static const int dy9[9] = {0, 0, 0, 1, 0, 1, 1, 0, 0}, dx9[9] = {0, 1, 0, 0, 0, 1, 0, 1, 0}, cl9[9] = {0, 1, 1, 2, 2, 3, 3, 3, 3};
-    bool ok = true;
-    for (int t = 0; t < 9; ++t) ok = ok && p.dy[t] == dy9[t] && p.dx[t] == dx9[t] && taps_host[4 * t + 3] == cl9[t];
-    for (int c = 0; c < 4; ++c) ok = ok && p.cls_ooh[c] == (c >> 1) && p.cls_oow[c] == (c & 1);
-    p.s2d = ok ? 1 : 0;
-  }
+  if (no_s2d) p.s2d = 0;
+  static const bool no_pipe = getenv("DGV2_NO_PIPE") != nullptr;   // A/B switch for benchmarking
   DGV2_DISPATCH_DTYPE(dtype, {
     rc = -2;
-    if ((!no_pipe || !plain) && wrap_ok) {
+    if ((!no_pipe || !plain) && wrap) {
       // four output classes quadruple the accumulators: 32-channel tiles keep them in registers
-      if (O <= 16) rc = dispatch_pipe<T, 16>(y, x, w, p, f33, st);
-      else if (O <= 32 || ncls == 4) rc = dispatch_pipe<T, 32>(y, x, w, p, f33, st);
+      if (p.O <= 16) rc = dispatch_pipe<T, 16>(y, x, w, p, f33, st);
+      else if (p.O <= 32 || p.ncls == 4) rc = dispatch_pipe<T, 32>(y, x, w, p, f33, st);
       else rc = dispatch_pipe<T, 64>(y, x, w, p, f33, st);
     }
     if (rc == -2) {
       if (!plain) return DGV2_ENOTSUP;
-      if (O <= 16) rc = launch_direct<T, 16>(y, x, w, p, st);
-      else if (O <= 32) rc = launch_direct<T, 32>(y, x, w, p, st);
+      if (p.O <= 16) rc = launch_direct<T, 16>(y, x, w, p, st);
+      else if (p.O <= 32) rc = launch_direct<T, 32>(y, x, w, p, st);
       else rc = launch_direct<T, 64>(y, x, w, p, st);
     }
   });
@@ -1094,53 +1079,82 @@ static int conv_taps_impl(void* y, int ldy, const void* x, const void* w, int B,
   DGV2_RETURN_LAST();
 }
 
-extern "C" int dgv2_conv_taps_ld(void* y, int ldy, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg,
-                                 int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w,
-                                 int out_stride, int ncls, const int* cls_host, int ntaps, int wtaps,
-                                 const int* taps_host, int nextra, const int* extras_host, int hzero, int ring,
-                                 int accumulate, const float* bias, const void* resid, int act, float alpha,
-                                 float scale, int dtype, void* stream) {
+bool conv_args_ok(const void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int k, int stride,
+                  int kstep) {
+  return y && x && w && B > 0 && H > 0 && W > 0 && Cin > 0 && O > 0 && (k == 1 || k == 3) && (stride == 1 || stride == 2) &&
+         Cin % kstep == 0 && aligned16(x) && aligned16(w);   // kstep: one 64-byte K-chunk of the contraction
+}
+
+}  // namespace
+
+// Contracts: include/dgv2.h.
+extern "C" int dgv2_conv_direct_fwd(void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int k,
+                                    int stride, const float* bias, const void* resid, int act, float alpha, float scale,
+                                    int dtype, void* stream) {
   if (dtype != DGV2_F32 && dtype != DGV2_BF16) return DGV2_EINVAL;
-  return conv_taps_impl(y, ldy, x, w, B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy, in_stride, ioff_h, ioff_w, out_stride, ncls,
-                        cls_host, ntaps, wtaps, taps_host, nextra, extras_host, hzero, ring, accumulate, bias, resid, act,
-                        alpha, scale, dtype, nullptr, stream);
+  if (!conv_args_ok(y, x, w, B, H, W, Cin, O, k, stride, dtype == DGV2_BF16 ? 32 : 16)) return DGV2_EINVAL;
+  if (act != 0 && act != 3) return DGV2_EINVAL;
+  DConv p = fwd_form(B, H, W, Cin, O, k, stride);
+  p.bias = bias; p.resid = resid; p.act = act; p.alpha = alpha; p.scale = scale;
+  return conv_launch(p, k == 3, y, x, w, dtype, (hipStream_t)stream);
 }
 
-// dgv2_conv_taps (single class, no extras, overwrite) on e4m3 operands: x8 [B,Hin,Win,Cin] and w8 [O,wtaps,Cin] are OCP
-// e4m3 bytes (x at unit scale, w scaled by a per-tensor power of two: dgv2_fp8_quant_weights), contracted by
-// v_mfma_f32_16x16x32_fp8_fp8 with fp32 accumulation;
-//   y (bf16) = act( acc * acc_scale[0] + resid + bias ) * scale,   acc_scale: DEVICE scalar (EqualLR factor / weight scale).
-// Cin % 64 == 0 (one 64-byte K-chunk = 64 channels), O >= 64; DGV2_ENOTSUP otherwise (callers then run the bf16 conv).
-extern "C" int dgv2_conv_taps_fp8(void* y, const void* x8, const void* w8, const float* acc_scale, int B, int Hin,
-                                  int Win, int Cin, int Hg, int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h,
-                                  int ioff_w, int ntaps, int wtaps, const int* taps_host, int ring, const float* bias,
-                                  const void* resid, int act, float alpha, float scale, void* stream) {
-  if (!taps_host || ntaps < 1 || ntaps > 9 || !acc_scale) return DGV2_EINVAL;
-  if (Cin % 64) return DGV2_ENOTSUP;
-  int taps4[36];
-  for (int t = 0; t < ntaps; ++t) {
-    taps4[4 * t] = taps_host[3 * t]; taps4[4 * t + 1] = taps_host[3 * t + 1]; taps4[4 * t + 2] = taps_host[3 * t + 2];
-    taps4[4 * t + 3] = 0;
-  }
-  const int cls[2] = {0, 0};
-  return conv_taps_impl(y, O, x8, w8, B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy, in_stride, ioff_h, ioff_w, 1, 1, cls, ntaps,
-                        wtaps, taps4, 0, nullptr, 0, ring, 0, bias, resid, act, alpha, scale, DGV2_FP8, acc_scale, stream);
+extern "C" int dgv2_conv_direct_fwd_fp8(void* y, const void* x8, const void* w8, const float* acc_scale, int B, int H,
+                                        int W, int Cin, int O, int k, int stride, const float* bias, const void* resid,
+                                        int act, float alpha, float scale, void* stream) {
+  if (!conv_args_ok(y, x8, w8, B, H, W, Cin, O, k, stride, 1) || !acc_scale || (act != 0 && act != 3)) return DGV2_EINVAL;
+  if (Cin % 64) return DGV2_ENOTSUP;   // one 64-byte K-chunk = 64 channels
+  DConv p = fwd_form(B, H, W, Cin, O, k, stride);
+  p.acc_scale = acc_scale;
+  p.bias = bias; p.resid = resid; p.act = act; p.alpha = alpha; p.scale = scale;
+  return conv_launch(p, k == 3, y, x8, w8, DGV2_FP8, (hipStream_t)stream);
 }
 
-// The single-class, no-extras form (taps_host: ntaps triples (dy, dx, widx)).
-extern "C" int dgv2_conv_taps(void* y, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg, int Wg,
-                              int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w, int out_stride,
-                              int ooff_h, int ooff_w, int ntaps, int wtaps, const int* taps_host, int hzero, int ring,
-                              int accumulate, const float* bias, const void* resid, int act, float alpha,
-                              float scale, int dtype, void* stream) {
-  if (!taps_host || ntaps < 1 || ntaps > 9) return DGV2_EINVAL;
-  int taps4[36];
-  for (int t = 0; t < ntaps; ++t) {
-    taps4[4 * t] = taps_host[3 * t]; taps4[4 * t + 1] = taps_host[3 * t + 1]; taps4[4 * t + 2] = taps_host[3 * t + 2];
-    taps4[4 * t + 3] = 0;
+extern "C" int dgv2_conv_direct_dgrad(void* gx, const void* gy, const void* wt, int B, int H, int W, int C, int O, int k,
+                                      int stride, const void* resid, int dtype, void* stream) {
+  if (dtype != DGV2_F32 && dtype != DGV2_BF16) return DGV2_EINVAL;
+  if (!conv_args_ok(gx, gy, wt, B, H, W, O, C, k, stride, dtype == DGV2_BF16 ? 32 : 16)) return DGV2_EINVAL;
+  if (stride == 2 && (k == 1 || (H & 1) || (W & 1))) return DGV2_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  static const bool fused = getenv("DGV2_NO_FUSED_DGRAD") == nullptr;   // A/B switch for benchmarking
+  const bool s1 = k == 3 && stride == 1;
+  DConv whole = stride == 2 ? dgrad_s2_form(B, H, W, C, O) : dgrad_s1_form(B, H, W, C, O, k);
+  if (s1) border_extras(whole);
+  // resid rides in the fused stride-1 3x3 launches only.  Whether those are taken is the wrap rule alone -- their halo tile
+  // (at most 12 x 34 pixels) fits every pipelined instance --, so the answer is known before the first launch
+  if (resid && !(s1 && fused && wrap_ok(whole))) return DGV2_ENOTSUP;
+  whole.resid = resid;
+  int rc = 0;
+  if (k == 1) return conv_launch(whole, false, gx, gy, wt, dtype, st);
+  const int tail = C % 64, es = dtype == DGV2_BF16 ? 2 : 4;
+  if (s1 && fused && C > 128 && (tail == 16 || tail == 32) && (int64_t)B * H * W <= 32768) {
+    // a channel count just past a multiple of the 64-channel slab (the epilogue conv's 513 inputs padded to 528 / 544) costs
+    // a whole extra round of blocks for a slab that is three quarters empty: the full slabs and the tail run as two launches
+    // into channel ranges of gx (ldy = C).  Only the first accepted: the whole launch below overwrites it
+    DConv part = whole;
+    part.ldy = C;
+    for (int ch0 = 0, n = C - tail; ch0 < C && rc == 0; ch0 += n, n = tail) {
+      part.O = n;
+      part.resid = resid ? (const char*)resid + (size_t)ch0 * es : nullptr;
+      rc = conv_launch(part, true, (char*)gx + (size_t)ch0 * es, gy, (const char*)wt + (size_t)ch0 * 9 * O * es, dtype, st);
+    }
+    if (rc != DGV2_ENOTSUP) return rc;
   }
-  const int cls[2] = {ooff_h, ooff_w};
-  return dgv2_conv_taps_ex(y, x, w, B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy, in_stride, ioff_h, ioff_w, out_stride, 1, cls,
-                           ntaps, wtaps, taps4, 0, nullptr, hzero, ring, accumulate, bias, resid, act, alpha, scale,
-                           dtype, stream);
+  if (fused) {
+    rc = conv_launch(whole, s1, gx, gy, wt, dtype, st);
+    if (rc != DGV2_ENOTSUP) return rc;
+  }
+  if (resid) return DGV2_ENOTSUP;   // (not reached: see above)
+  // The unfused sequences, for geometries only the synchronous kernel covers (it has neither classes nor extras)
+  if (s1) {   // the main launch, then one accumulate launch per replicate row
+    whole.nx = 0; whole.border_ok = 0;
+    if ((rc = conv_launch(whole, true, gx, gy, wt, dtype, st))) return rc;
+    if ((rc = conv_launch(dgrad_s1_row_form(B, H, W, C, O, 0), false, gx, gy, wt, dtype, st))) return rc;
+    return conv_launch(dgrad_s1_row_form(B, H, W, C, O, 1), false, gx, gy, wt, dtype, st);
+  }
+  for (int c = 0; c < 4; ++c)   // one launch per parity class, then the top border of the classes (0, pw)
+    if ((rc = conv_launch(dgrad_s2_class_form(B, H, W, C, O, c >> 1, c & 1, 0), false, gx, gy, wt, dtype, st))) return rc;
+  for (int pw = 0; pw < 2; ++pw)
+    if ((rc = conv_launch(dgrad_s2_class_form(B, H, W, C, O, 0, pw, 1), false, gx, gy, wt, dtype, st))) return rc;
+  return 0;
 }

@@ -307,39 +307,21 @@ __global__ __launch_bounds__(256, RESID ? 2 : 3) void conv3x3_strip_kernel(bf16_
 
 }  // namespace
 
-// Called by dgv2_conv_taps_ex (conv_direct.hip) for the geometries documented there.  Returns -2 when this kernel does
-// not cover the call (the generic engine then runs it).
-int dgv2_conv_strip_try(void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int ntaps, int wtaps,
-                        const int* taps4, int nextra, const int* extras5, int hzero, const float* bias,
-                        const void* resid, int act, float alpha, float scale, hipStream_t st) {
+// Called by conv_launch (conv_direct.hip) for the full 3x3 grid at stride 1: tap (dy, dx) reads weight slot
+// widx0 + ((dy + 1) * 3 + dx + 1) * wstep of w [O][wtaps][32]; border (hzero only): add the replicate-padding terms of the
+// stride-1 data gradient (rows 0 / H-1, dy = 0, the weights of dy = +1 / -1).  Returns -2 when this kernel does not
+// cover the call (the generic engine then runs it).
+int dgv2_conv_strip_try(void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int wtaps, int widx0,
+                        int wstep, int border, int hzero, const float* bias, const void* resid, int act, float alpha,
+                        float scale, hipStream_t st) {
   static const bool off = getenv("DGV2_NO_STRIP") != nullptr;   // A/B switch for benchmarking
-  if (off || Cin != S_C || O != S_C || ntaps != 9 || wtaps < 9 || (W & 31) || (H & 7) || H < 16 || W < 32) return -2;
+  if (off || Cin != S_C || O != S_C || wtaps < 9 || (W & 31) || (H & 7) || H < 16 || W < 32) return -2;
   if (B <= 0 || (int64_t)B * H * W * S_C >= (1LL << 40)) return -2;
+  if (border && !hzero) return -2;
   SGeom g;
   g.B = B; g.H = H; g.W = W; g.wtaps = wtaps;
-  for (int t = 0; t < 9; ++t) g.widx[t] = -1;
-  for (int t = 0; t < 9; ++t) {
-    const int dy = taps4[4 * t], dx = taps4[4 * t + 1], wi = taps4[4 * t + 2];
-    if (dy < -1 || dy > 1 || dx < -1 || dx > 1 || taps4[4 * t + 3] != 0) return -2;
-    g.widx[(dy + 1) * 3 + dx + 1] = wi;
-  }
-  for (int t = 0; t < 9; ++t)
-    if (g.widx[t] < 0) return -2;
-  g.border = 0;
-  if (nextra) {
-    // exactly the replicate-padding terms of the stride-1 data gradient: rows 0 / H-1, dy = 0, the weights of dy = +1 / -1
-    if (!hzero || nextra != 6) return -2;
-    int seen = 0;
-    for (int e = 0; e < 6; ++e) {
-      const int* q = extras5 + 5 * e;
-      if (q[0] != 0 || q[1] < -1 || q[1] > 1 || q[3] != 0) return -2;
-      if (q[4] == 0 && q[2] == g.widx[6 + q[1] + 1]) seen |= 1 << (q[1] + 1);
-      else if (q[4] == H - 1 && q[2] == g.widx[q[1] + 1]) seen |= 8 << (q[1] + 1);
-      else return -2;
-    }
-    if (seen != 63) return -2;
-    g.border = 1;
-  }
+  for (int t = 0; t < 9; ++t) g.widx[t] = widx0 + t * wstep;
+  g.border = border;
   g.bias = bias; g.resid = (const bf16_t*)resid; g.act = act; g.alpha = alpha; g.scale = scale;
   const size_t lds = sizeof(uint4) * S_RING * S_ROWSLOTS + sizeof(float) * S_C;   // 52,224 B ring + bias
   dim3 grid(B * (W >> 5));

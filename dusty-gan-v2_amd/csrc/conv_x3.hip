@@ -580,7 +580,7 @@ int launch_x3(float* y, const float* x, const bf16_t* wimg, CX3 p, hipStream_t s
 // trunk widened to fp32: the discriminator's features in front of its fp32 epilogue) -- their m and l planes are zero, so
 // their three products are not issued: the same sum at half the MFMAs.  A value that breaks the promise raises
 // bit DGV2_STATUS_X_INEXACT of *status (the caller's device word; required when x_exact > 0).  0: no promise.
-// DGV2_ENOTSUP where the kernel does not cover the geometry (callers then run dgv2_conv_taps in fp32).
+// DGV2_ENOTSUP where the kernel does not cover the geometry (callers then run dgv2_conv_direct_fwd in fp32).
 extern "C" int dgv2_conv3x3_x3_fwd(void* y, const void* x, const void* w3, int B, int H, int W, int Cx, int x_exact, int O,
                                    const float* bias, const void* resid, int act, float alpha, float scale, int* status,
                                    void* stream) {
@@ -629,7 +629,7 @@ extern "C" int dgv2_conv3x3_x3_dgrad(void* gx, const void* gy, const void* w3t, 
   DGV2_RETURN_LAST();
 }
 
-// The plane images of both entries above from weight VALUES w [O, 9, Cp] fp32 (what dgv2_conv_taps takes) -- for passes
+// The plane images of both entries above from weight VALUES w [O, 9, Cp] fp32 (what dgv2_conv_direct_fwd takes) -- for passes
 // that do not run on the weight bank.  w3 [3][O / 64][ceil(Cp / 32)][2304 units], w3t [3][Cp / 64][O / 32][2304 units]; either
 // may be NULL.  O % 64 == 0, Cp % 8 == 0, Cp >= 64.
 extern "C" int dgv2_conv_x3_images(void* w3, void* w3t, const void* w, int O, int Cp, void* stream) {

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE
 
 F32, BF16 = 0, 1
 F16 = 3   # the dgv2_seg_loss_* entries and dgv2_fire_fwd only
-ABI_VERSION = 58
+ABI_VERSION = 59
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -79,7 +79,7 @@ SIGNATURES = {
     "dgv2_resample_tab_q8": [_c_ptr] * 5 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr],
     "dgv2_fp8_quant_weights": [_c_ptr] * 6 + [_c_int] + [_c_ptr] * 3,
     "dgv2_fp8_dequant": [_c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr],
-    "dgv2_conv_taps_fp8": [_c_ptr] * 4 + [_c_int] * 14 + [_c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_ptr],
+    "dgv2_conv_direct_fwd_fp8": [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_ptr],
     "dgv2_modconv_up_t": [_c_ptr] * 5 + [_c_f32] + [_c_int] * 9 + [_c_ptr],
     "dgv2_up2_lag_sumsq": [_c_ptr] * 5 + [_c_int] * 5 + [_c_ptr, _c_int, _c_ptr, _c_ptr],
     "dgv2_resample_tab_actbwd_scratch": [_c_ptr] + [_c_int] * 6,
@@ -113,12 +113,8 @@ SIGNATURES = {
     "dgv2_mod_prep_bwd": [_c_ptr] * 11 + [_c_int] * 9 + [_c_ptr],
     "dgv2_sum_squares": [_c_ptr, _c_ptr, _c_i64, _c_int, _c_int, _c_int, _c_ptr],
     "dgv2_conv_fwd": [_c_ptr] * 3 + [_c_int] * 10 + [_c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
-    "dgv2_conv_taps": [_c_ptr] * 3 + [_c_int] * 17 + [_c_ptr] + [_c_int] * 3 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int,
-                                                                               _c_ptr],
-    "dgv2_conv_taps_ex": [_c_ptr] * 3 + [_c_int] * 14 + [_c_ptr, _c_int, _c_int, _c_ptr, _c_int, _c_ptr] + [_c_int] * 3
-    + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
-    "dgv2_conv_taps_ld": [_c_ptr, _c_int, _c_ptr, _c_ptr] + [_c_int] * 14 + [_c_ptr, _c_int, _c_int, _c_ptr, _c_int, _c_ptr] + [_c_int] * 3
-    + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
+    "dgv2_conv_direct_fwd": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr, _c_ptr, _c_int, _c_f32, _c_f32, _c_int, _c_ptr],
+    "dgv2_conv_direct_dgrad": [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr, _c_int, _c_ptr],
     "dgv2_conv_wgrad_direct": [_c_ptr] * 3 + [_c_int] * 10 + [_c_ptr],
     "dgv2_conv1x1_fwd": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr],
     "dgv2_conv1x1_dgrad": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr],

@@ -37,44 +37,7 @@ def _kstep(t):
     return 32 if t.dtype == torch.bfloat16 else 16
 
 
-def _conv_taps(y, x, w3, Hg, Wg, in_stride, ioff, out_stride, ooff, taps, hzero, accumulate=False,
-               bias=None, act=0, alpha=0.2, scale=1.0, resid=None):
-    """Direct halo-tile conv with a tap list (dgv2_conv_taps).  x [B,Hin,Win,Cin]; w3 [O,wtaps,Cin];
-    y [B,Hy,Wy,O]; taps: list of (dy, dx, widx)."""
-    B, Hin, Win, Cin = x.shape
-    O, wtaps, _ = w3.shape
-    _, Hy, Wy, _ = y.shape
-    arr = (_ct.c_int * (3 * len(taps)))(*[v for t in taps for v in t])
-    N.call("dgv2_conv_taps", N.ptr(y), N.ptr(x), N.ptr(w3), B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy, in_stride,
-           ioff[0], ioff[1], out_stride, ooff[0], ooff[1], len(taps), wtaps, arr, int(hzero), 1, int(accumulate),
-           N.ptr(bias), N.ptr(resid), act, alpha, scale, _dt(x), N.stream())
-
-
-_FUSED_DGRAD = os.environ.get("DGV2_NO_FUSED_DGRAD") is None   # A/B switch for benchmarking
-
-
 _S2D8 = os.environ.get("DGV2_NO_S2D8") is None                 # A/B switch: stride-2 data gradients on conv8_s2d.hip
-
-
-def _conv_taps_ex(y, x, w3, Hg, Wg, in_stride, ioff, out_stride, classes, taps4, extras, hzero, resid=None, ch0=None):
-    """dgv2_conv_taps_ex: output classes [(ooff_h, ooff_w)], taps [(dy, dx, widx, cls)] sorted by class, border
-    extras [(dy, dx, widx, cls, row)].  Returns False when the engine asks for the per-class fallback.
-    ch0: write the O = w3.shape[0] output channels at channel offset ch0 of the wider tensor y (dgv2_conv_taps_ld)."""
-    B, Hin, Win, Cin = x.shape
-    O, wtaps, _ = w3.shape
-    _, Hy, Wy, ldy = y.shape
-    carr = (_ct.c_int * (2 * len(classes)))(*[v for c in classes for v in c])
-    tarr = (_ct.c_int * (4 * len(taps4)))(*[v for t in taps4 for v in t])
-    earr = (_ct.c_int * max(5 * len(extras), 1))(*[v for e in extras for v in e])
-    if ch0 is not None:
-        es = y.element_size()
-        rp = None if resid is None else resid.data_ptr() + ch0 * es
-        return N.try_call("dgv2_conv_taps_ld", y.data_ptr() + ch0 * es, ldy, N.ptr(x), N.ptr(w3), B, Hin, Win, Cin, Hg, Wg,
-                          O, Hy, Wy, in_stride, ioff[0], ioff[1], out_stride, len(classes), carr, len(taps4), wtaps,
-                          tarr, len(extras), earr, int(hzero), 1, 0, None, rp, 0, 0.2, 1.0, _dt(x), N.stream())
-    return N.try_call("dgv2_conv_taps_ex", N.ptr(y), N.ptr(x), N.ptr(w3), B, Hin, Win, Cin, Hg, Wg, O, Hy, Wy,
-                      in_stride, ioff[0], ioff[1], out_stride, len(classes), carr, len(taps4), wtaps, tarr,
-                      len(extras), earr, int(hzero), 1, 0, None, N.ptr(resid), 0, 0.2, 1.0, _dt(x), N.stream())
 
 
 def _direct_ok(g, cin):
@@ -161,21 +124,14 @@ def _conv_fwd_raw(x, w, g, bias=None, act=0, alpha=0.2, scale=1.0, resid=None, w
     if _is_1x1(g) and bias is None and act == 0 and _conv1x1("dgv2_conv1x1_fwd", y, x, w, B, H * W, C, O, resid):
         return y     # the residual blocks' skip conv: a plain GEMM, no halo tiles (conv1x1.hip)
     if _direct_ok(g, C % _kstep(x) == 0):
-        taps = [(ky - g.pad, kx - g.pad, ky * g.kw + kx) for ky in range(g.kh) for kx in range(g.kw)]
-        _conv_taps(y, x, w.reshape(O, g.kh * g.kw, C), Ho, Wo, g.stride, (0, 0), 1, (0, 0), taps, False,
-                   bias=bias, act=act, alpha=alpha, scale=scale, resid=resid)
+        N.call("dgv2_conv_direct_fwd", N.ptr(y), N.ptr(x), N.ptr(w), B, H, W, C, O, g.kh, g.stride, N.ptr(bias), N.ptr(resid),
+               act, alpha, scale, _dt(x), N.stream())
         return y
     if resid is not None:
         raise RuntimeError("dgv2: fused residual needs the direct conv engine (ring padding, Cin % K-step == 0)")
     N.call("dgv2_conv_fwd", N.ptr(y), N.ptr(x), N.ptr(w), B, H, W, C, O, g.kh, g.kw, g.stride, g.pad, g.ring,
            N.ptr(bias), act, alpha, scale, _dt(x), N.stream())
     return y
-
-
-def _axis_taps_s2(parity):
-    """Stride-2, pad-1, 3-tap transpose along one axis for output parity `parity`:
-    list of (offset into gy, kernel index)."""
-    return [(0, 1)] if parity == 0 else [(1, 0), (0, 2)]
 
 
 def _conv_dgrad8(gy, w8t, xshape, resid):
@@ -189,69 +145,23 @@ def _conv_dgrad8(gy, w8t, xshape, resid):
 
 
 def _conv_dgrad_direct(gy, wt3, g, xshape, resid=None):
-    """Data gradient on the direct engine: gy [B,Ho,Wo,O], wt3 [C,kh*kw,O] -> gx [B,H,W,C] (+ resid, the gradient
-    of a sibling branch of the same input, added in the epilogue of the one-launch stride-1 path).
-    Circular W padding transposes to a wrap of the gy coordinate; the replicate rows of the H padding
-    add one-row border terms (accumulate launches)."""
-    if resid is not None and not (_FUSED_DGRAD and g.kh == 3 and g.stride == 1):
-        return _conv_dgrad_direct(gy, wt3, g, xshape) + resid
+    """Data gradient on the direct engine (dgv2_conv_direct_dgrad): gy [B,Ho,Wo,O], wt3 [C,kh*kw,O] -> gx [B,H,W,C], the
+    replicate-row border terms included.  resid (the gradient of a sibling branch of the same input) is added in the
+    epilogue of the one-launch stride-1 3x3 path; where the library cannot fold it, it is added here."""
     B, H, W, C = xshape
     gx = torch.empty(xshape, device=gy.device, dtype=gy.dtype)
-    k = g.kh
-    if k == 1:
-        _conv_taps(gx, gy, wt3, H, W, 1, (0, 0), 1, (0, 0), [(0, 0, 0)], True)
-        return gx
-    if g.stride == 1:
-        taps = [(1 - ky, 1 - kx, ky * 3 + kx) for ky in range(3) for kx in range(3)]
-        # one launch: the replicate rows ride along as border extras of output rows 0 and H-1
-        extras = [(0, 1 - kx, kx, 0, 0) for kx in range(3)] + [(0, 1 - kx, 6 + kx, 0, H - 1) for kx in range(3)]
-        tail = C % 64
-        if _FUSED_DGRAD and C > 128 and tail in (16, 32) and B * H * W <= 32768:
-            # a channel count just past a multiple of the 64-channel slab (the epilogue conv's 513 inputs padded to 528 /
-            # 544) costs a whole extra round of blocks for a slab that is three quarters empty: run the full slabs and
-            # the tail as two launches into channel ranges of gx
-            main = C - tail
-            t4 = [t + (0,) for t in taps]
-            if (_conv_taps_ex(gx, gy, wt3[:main], H, W, 1, (0, 0), 1, [(0, 0)], t4, extras, True, resid=resid, ch0=0)
-                    and _conv_taps_ex(gx, gy, wt3[main:], H, W, 1, (0, 0), 1, [(0, 0)], t4, extras, True, resid=resid,
-                                      ch0=main)):
-                return gx
-        if _FUSED_DGRAD and _conv_taps_ex(gx, gy, wt3, H, W, 1, (0, 0), 1, [(0, 0)], [t + (0,) for t in taps], extras,
-                                          True, resid=resid):
-            return gx
-        if resid is not None:
-            return _conv_dgrad_direct(gy, wt3, g, xshape) + resid
-        _conv_taps(gx, gy, wt3, H, W, 1, (0, 0), 1, (0, 0), taps, True)
-        # replicate-padding rows: padded row -1 (-> h = 0) is read by ky = 0 of output row 0,
-        # padded row H (-> h = H-1) by ky = 2 of output row H-1
-        _conv_taps(gx, gy, wt3, 1, W, 1, (0, 0), 1, (0, 0), [(0, 1 - kx, kx) for kx in range(3)], True, True)
-        _conv_taps(gx, gy, wt3, 1, W, 1, (H - 1, 0), 1, (H - 1, 0), [(0, 1 - kx, 6 + kx) for kx in range(3)], True,
-                   True)
-        return gx
     # stride 2, deeper blocks (C a multiple of 128): the eight-wave engine, one launch per output row parity
-    if _S2D8 and gy.dtype == torch.bfloat16 and g.ring and C % 128 == 0 and wt3.is_contiguous():
-        if N.try_call("dgv2_conv3x3_s2_dgrad8", N.ptr(gx), N.ptr(gy), N.ptr(wt3), B, H // 2, W // 2, C, gy.shape[3], _dt(gy),
-                      N.stream()):
-            return gx
-    # stride 2: the four output parity classes (only the taps each class can see) and the top border in one launch
-    classes, taps4, extras = [], [], []
-    for ph in (0, 1):
-        for pw in (0, 1):
-            c = len(classes)
-            classes.append((ph, pw))
-            taps4 += [(dy, dx, ky * 3 + kx, c) for dy, ky in _axis_taps_s2(ph) for dx, kx in _axis_taps_s2(pw)]
-            if ph == 0:
-                extras += [(0, dx, kx, c, 0) for dx, kx in _axis_taps_s2(pw)]
-    if _FUSED_DGRAD and _conv_taps_ex(gx, gy, wt3, H // 2, W // 2, 1, (0, 0), 2, classes, taps4, extras, True):
+    if (g.stride == 2 and resid is None and _S2D8 and gy.dtype == torch.bfloat16 and g.ring and C % 128 == 0
+            and wt3.is_contiguous()
+            and N.try_call("dgv2_conv3x3_s2_dgrad8", N.ptr(gx), N.ptr(gy), N.ptr(wt3), B, H // 2, W // 2, C, gy.shape[3],
+                           _dt(gy), N.stream())):
         return gx
-    for ph in (0, 1):
-        for pw in (0, 1):
-            taps = [(dy, dx, ky * 3 + kx) for dy, ky in _axis_taps_s2(ph) for dx, kx in _axis_taps_s2(pw)]
-            _conv_taps(gx, gy, wt3, H // 2, W // 2, 1, (0, 0), 2, (ph, pw), taps, True)
-    for pw in (0, 1):  # padded row -1 (-> h = 0) is read by ky = 0 of output row 0
-        taps = [(0, dx, kx) for dx, kx in _axis_taps_s2(pw)]
-        _conv_taps(gx, gy, wt3, 1, W // 2, 1, (0, 0), 2, (0, pw), taps, True, True)
-    return gx
+    if N.try_call("dgv2_conv_direct_dgrad", N.ptr(gx), N.ptr(gy), N.ptr(wt3), B, H, W, C, gy.shape[3], g.kh, g.stride,
+                  N.ptr(resid), _dt(gy), N.stream()):
+        return gx
+    if resid is None:
+        raise RuntimeError("dgv2_conv_direct_dgrad refused a call without a residual")
+    return _conv_dgrad_direct(gy, wt3, g, xshape) + resid
 
 
 def _conv_dgrad_raw(gy, w, g, xshape, wt=None, resid=None, w8t=None):
@@ -1089,5 +999,5 @@ def conv_resid_ok(x, geom):
 __all__ = ["ConvGeom", "x3_auto", "PreparedConv", "ConvEpilogue", "linear_low", "gemm_x3", "linear_f32", "d_tail_ok",
            "d_tail", "mbstd_cat_ok", "mbstd_cat", "flatten_nchw", "scaled_handle", "conv8t_image_ok", "conv8_image_ok",
            "convx3_image_ok", "convx3t_image_ok", "conv_weight_bank", "conv_ring_ep", "conv_ring", "conv_resid_ok",
-           "_conv_taps", "_conv_fwd_raw", "_conv_dgrad_direct", "_conv_dgrad_raw", "_bmm_tn_small", "_conv_wgrad_raw",
+           "_conv_fwd_raw", "_conv_dgrad_direct", "_conv_dgrad_raw", "_bmm_tn_small", "_conv_wgrad_raw",
            "_resample_actbwd", "_Conv"]

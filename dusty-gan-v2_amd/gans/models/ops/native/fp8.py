@@ -73,7 +73,7 @@ def _resample_q8_raw(x, spec, in_hw):
 
 
 def fp8_ok(x, cout):
-    """e4m3 operands need whole 64-channel K-chunks and >= 64 output channels (dgv2_conv_taps_fp8), bf16 activations."""
+    """e4m3 operands need whole 64-channel K-chunks and >= 64 output channels (dgv2_conv_direct_fwd_fp8), bf16 activations."""
     return bool(x.is_cuda and x.dtype == torch.bfloat16 and x.shape[3] % 64 == 0 and cout >= 64)
 
 
@@ -107,11 +107,9 @@ def _conv_fwd_fp8(x8, w8, descale, g, bias=None, act=0, alpha=0.2, scale=1.0, re
     O = w8.shape[0]
     Ho, Wo = g.out_hw(H, W)
     y = torch.empty((B, Ho, Wo, O), device=x8.device, dtype=torch.bfloat16)
-    taps = [(ky - g.pad, kx - g.pad, ky * g.kw + kx) for ky in range(g.kh) for kx in range(g.kw)]
-    arr = (_ct.c_int * (3 * len(taps)))(*[v for t in taps for v in t])
     N.check(x8, w8, bias, resid)
-    N.call("dgv2_conv_taps_fp8", N.ptr(y), N.ptr(x8), N.ptr(w8), N.ptr(descale), B, H, W, C, Ho, Wo, O, Ho, Wo, g.stride, 0,
-           0, len(taps), g.kh * g.kw, arr, 1, N.ptr(bias), N.ptr(resid), act, alpha, scale, N.stream())
+    N.call("dgv2_conv_direct_fwd_fp8", N.ptr(y), N.ptr(x8), N.ptr(w8), N.ptr(descale), B, H, W, C, O, g.kh, g.stride,
+           N.ptr(bias), N.ptr(resid), act, alpha, scale, N.stream())
     return y
 
 

@@ -553,14 +553,14 @@ int dgv2_conv_weight_bank_ex(void* const* wf, void* const* wt, void* const* w8, 
  * replaces: ops.Conv2d forward (gans/models/ops/common.py:187-210) at ResidualBlock.conv1 / .conv2
  * (gans/models/dusty_v2.py:325-345).  DGV2_ENOTSUP where the engine does not cover the geometry (O % 64 (stride 1) /
  * O % 128 (stride 2), Cin % 32, Cin >= 64, at least 4 output rows and 32 / 64 output columns): callers then run
- * dgv2_conv_taps on wf. */
+ * dgv2_conv_direct_fwd on wf. */
 int dgv2_conv3x3_fwd8(void* y, const void* x, const void* w8, int B, int Hin, int Win, int Cin, int O, int stride,
                       const float* bias, const void* resid, int act, float alpha, float scale, int dtype, void* stream);
 /* The stride-1 data gradient of the same conv on the transposed image w8t: gx [B,H,W,C] (bf16) from gy [B,H,W,O], the
  * replicate-row terms of rows 0 and H - 1 included, + resid (the gradient of a sibling branch of the same input, like gx,
  * or NULL).  replaces: the cuDNN data gradient autograd calls for ops.Conv2d (common.py:187-210) at ResidualBlock.conv1
  * (dusty_v2.py:329).  DGV2_ENOTSUP where the engine does not cover the geometry (C % 64, O % 32, O >= 64, H >= 8,
- * W >= 32 / 64): callers then run dgv2_conv_taps_ex on wt. */
+ * W >= 32 / 64): callers then run dgv2_conv_direct_dgrad on wt. */
 int dgv2_conv3x3_dgrad8(void* gx, const void* gy, const void* w8t, int B, int H, int W, int C, int O, const void* resid,
                         int dtype, void* stream);
 /* The STRIDE-2 data gradient of the 3x3 ring conv (pad 1) on the eight-wave engine (conv8_s2d.hip), from the transposed row
@@ -569,7 +569,7 @@ int dgv2_conv3x3_dgrad8(void* gx, const void* gy, const void* w8t, int B, int H,
  * tiles where those fill the chip, one four-class launch on four-row tiles otherwise.
  * replaces: the cuDNN data gradient autograd calls for ops.Conv2d (common.py:187-210) at ResidualBlock.conv2
  * (dusty_v2.py:337-345).  DGV2_ENOTSUP where the engine does not cover the geometry (C % 128, O % 32, O >= 64, Hg % 4,
- * Wg % 32, DGV2_BF16): callers then run dgv2_conv_taps_ex on wt. */
+ * Wg % 32, DGV2_BF16): callers then run dgv2_conv_direct_dgrad on wt. */
 int dgv2_conv3x3_s2_dgrad8(void* gx, const void* gy, const void* wt, int B, int Hg, int Wg, int C, int O, int dtype,
                            void* stream);
 
@@ -581,7 +581,7 @@ int dgv2_conv3x3_s2_dgrad8(void* gx, const void* gy, const void* wt, int B, int 
  *   resid like y or NULL.
  * replaces: ops.Conv2d(ch(4) + 1, ch(4), 3, 1, 1, ring) + FusedLeakyReLU of Discriminator.epilogue
  * (gans/models/dusty_v2.py:376-379) in the fp32 island of Discriminator.forward (:394-395).  DGV2_ENOTSUP where the
- * kernel does not cover the geometry (W % 32, Cx % 8, Cx >= 64, O % 64): callers then run dgv2_conv_taps in fp32. */
+ * kernel does not cover the geometry (W % 32, Cx % 8, Cx >= 64, O % 64): callers then run dgv2_conv_direct_fwd in fp32. */
 int dgv2_conv3x3_x3_fwd(void* y, const void* x, const void* w3, int B, int H, int W, int Cx, int x_exact, int O,
                         const float* bias, const void* resid, int act, float alpha, float scale, int* status,
                         void* stream);
@@ -609,7 +609,7 @@ int dgv2_conv3x3_x3_wgrad(float* gw, float* scratch, int64_t scratch_elems, cons
                           int W, int C, int clive, int x_exact, int O, float scale, int param_layout, int* status,
                           void* stream);
 int dgv2_conv3x3_x3_wgrad_scratch(int64_t* elems, int B, int H, int W, int C, int clive, int O);
-/* Both image sets from weight VALUES w [O, 9, Cp] fp32 (the operand layout of dgv2_conv_taps), for passes that do not
+/* Both image sets from weight VALUES w [O, 9, Cp] fp32 (the operand layout of dgv2_conv_direct_fwd), for passes that do not
  * run on the weight bank (R1's double backward): w3 [3][O / 64][ceil(Cp / 32)][2304 units of 8 bf16], w3t
  * [3][Cp / 64][O / 32][2304 units]; either may be NULL.  O % 64 == 0, Cp % 8 == 0, Cp >= 64. */
 int dgv2_conv_x3_images(void* w3, void* w3t, const void* w, int O, int Cp, void* stream);
@@ -629,56 +629,42 @@ int dgv2_conv_wgrad_stream_pl(float* gw, float* scratch, int64_t scratch_elems, 
                               int B, int H, int W, int C, int O, int k, int stride, int pad, int ring,
                               float scale, int param_layout, int dtype, void* stream);
 
-/* Direct (LDS halo-tile) convolution with a generic tap list -- the hot-path engine for the
- * discriminator convs and their data gradients (same reference lines as dgv2_conv_*):
- *   y[b, gh*out_stride+ooff_h, gw*out_stride+ooff_w, o] (=|+=) act( sum_t sum_c
- *       x[b, H(gh*in_stride+ioff_h+dy_t), W(gw*in_stride+ioff_w+dx_t), c] * w[o, widx_t, c] + bias[o] )
- * for gh < Hg, gw < Wg.  x [B,Hin,Win,Cin], w [O,wtaps,Cin], y [B,Hy,Wy,O].
- * taps_host: HOST pointer to ntaps (<= 9) triples (dy, dx, widx).  H(): clamp (hzero = 0, replicate
- * padding) or zero outside [0,Hin) (hzero = 1, gradients); W(): wrap (ring = 1) or clamp.
- * forward conv: taps (ky-pad, kx-pad), in_stride = stride; stride-1 dgrad: taps (1-ky, 1-kx) on gy
- * with transposed weights; stride-2 dgrad: one launch per output parity class (out_stride = 2);
- * replicate-row border terms: one-row launches with accumulate = 1.
- * Cin must be a multiple of 32 (bf16) / 16 (fp32).  resid (optional, layout of y) is added to the
- * accumulator before bias / activation: the residual sum of ResidualBlock (dusty_v2.py:343-345) costs
- * no extra pass. */
-int dgv2_conv_taps(void* y, const void* x, const void* w, int B, int Hin, int Win, int Cin,
-                   int Hg, int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w,
-                   int out_stride, int ooff_h, int ooff_w, int ntaps, int wtaps, const int* taps_host,
-                   int hzero, int ring, int accumulate, const float* bias, const void* resid, int act,
-                   float alpha, float scale, int dtype, void* stream);
-/* The general form: OUTPUT CLASSES and BORDER EXTRAS, so that a whole data gradient is one launch.
- *   taps_host   ntaps quadruples (dy, dx, widx, cls) sorted by cls; class c is written at
- *               (gh*out_stride + cls_host[2c], gw*out_stride + cls_host[2c+1]); ncls in {1, 4}
- *               (4 = the parity classes of the stride-2 data gradient: the gy halo tile and all nine
- *               weight taps are staged once instead of once per class);
- *   extras_host nextra <= 6 quintuples (dy, dx, widx, cls, row): one more tap for output row gh == row
- *               only -- the replicate-padding rows of the H border (dusty_v2.py Pad / common.py:10-24)
- *               fold into the same launch instead of one-row accumulate launches.
- * Returns DGV2_ENOTSUP when the geometry needs the synchronous fallback kernel, which has neither
- * (callers then issue one dgv2_conv_taps launch per class / border row). */
-int dgv2_conv_taps_ex(void* y, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg,
-                      int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w,
-                      int out_stride, int ncls, const int* cls_host, int ntaps, int wtaps,
-                      const int* taps_host, int nextra, const int* extras_host, int hzero, int ring,
-                      int accumulate, const float* bias, const void* resid, int act, float alpha,
-                      float scale, int dtype, void* stream);
-/* dgv2_conv_taps_ex whose O output channels are written into rows of ldy >= O channels (y / resid point at the first
- * of them), so that one launch can produce a channel range of a wider tensor. */
-int dgv2_conv_taps_ld(void* y, int ldy, const void* x, const void* w, int B, int Hin, int Win, int Cin, int Hg,
-                      int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w, int out_stride, int ncls,
-                      const int* cls_host, int ntaps, int wtaps, const int* taps_host, int nextra,
-                      const int* extras_host, int hzero, int ring, int accumulate, const float* bias,
-                      const void* resid, int act, float alpha, float scale, int dtype, void* stream);
+/* Direct (LDS halo-tile) convolution on the matrix cores (conv_direct.hip) -- the hot-path engine for the discriminator
+ * convs and their data gradients.  The caller states the conv; the library chooses the kernel (strip, eight-wave,
+ * image pairs, pipelined, synchronous) and builds its parameters.  Common to the three entries: channels-last tensors,
+ * k in {1, 3} with pad (k - 1) / 2, stride in {1, 2}, ring (circular) padding along W and replicate padding along H
+ * (common.py:10-24) -- nothing padded is materialised --, 16-byte aligned operands, contraction length (Cin forward, O in
+ * the data gradient) a multiple of one 64-byte K-chunk (32 bf16 / 16 fp32 / 64 e4m3 values).  DGV2_EINVAL otherwise.
+ *
+ * Forward:  y [B,Ho,Wo,O] = act( conv(x [B,H,W,Cin], w [O,k*k,Cin]) + resid + bias ) * scale,  Ho = (H + 2 pad - k) / stride + 1,
+ *   act 0 | 3 (leaky ReLU with `alpha`), bias [O] fp32 or NULL, resid like y or NULL (the residual sum of ResidualBlock,
+ *   dusty_v2.py:343-345, costs no extra pass).  dtype DGV2_F32 | DGV2_BF16.
+ * replaces: ops.Conv2d forward (gans/models/ops/common.py:187-210) at gans/models/dusty_v2.py:325-385. */
+int dgv2_conv_direct_fwd(void* y, const void* x, const void* w, int B, int H, int W, int Cin, int O, int k, int stride,
+                         const float* bias, const void* resid, int act, float alpha, float scale, int dtype, void* stream);
+/* The whole data gradient of that conv:  gx [B,H,W,C] from gy [B,Ho,Wo,O] and the transposed weights wt [C,k*k,O], the
+ * replicate-row terms of the H border included.  One launch where the pipelined kernel covers the geometry (stride 1:
+ * the border rows re-weighted in place, a channel count just past a multiple of 64 as two channel ranges; stride 2: the
+ * four output parity classes and the top border together), else the same sums as a sequence of launches (stride 1: main
+ * + two one-row accumulate launches; stride 2: four classes + two top-border launches).  stride 2 needs k == 3 and even
+ * H, W (DGV2_EINVAL).
+ * resid (like gx, or NULL: the gradient of a sibling branch of the same input) is added in the epilogue of the fused
+ * stride-1 3x3 form ONLY.  Where it cannot be folded -- k == 1, stride 2, or a geometry that form does not cover -- the
+ * entry returns DGV2_ENOTSUP before anything is launched and gx is untouched: call again with resid = NULL and add it.
+ * With resid = NULL the entry never answers DGV2_ENOTSUP.  DGV2_NO_FUSED_DGRAD (environment, A/B benchmarking) forces the
+ * launch sequences.
+ * replaces: the cuDNN data gradient autograd calls for ops.Conv2d (common.py:187-210) at dusty_v2.py:325-385. */
+int dgv2_conv_direct_dgrad(void* gx, const void* gy, const void* wt, int B, int H, int W, int C, int O, int k, int stride,
+                           const void* resid, int dtype, void* stream);
 
 /* The 1x1 stride-1 conv as a streaming GEMM over the B * P pixels (conv1x1.hip: the slab's weights stay in LDS, the
  * activations go from 16-byte global loads straight into the matrix cores, K ascending in one fp32 accumulator, the
- * residual added to the rounded product: bit for bit what dgv2_conv_taps computes for the same operands):
+ * residual added to the rounded product: bit for bit what dgv2_conv_direct_fwd / _dgrad compute for the same operands):
  *   dgv2_conv1x1_fwd:    y [B,P,O]  = x [B,P,C]  . wf [O,C]^T (+ resid [B,P,O])
  *   dgv2_conv1x1_dgrad:  gx [B,P,C] = gy [B,P,O] . wt [C,O]^T (+ resid [B,P,C])
  * wf / wt: the weight bank's forward / transposed layouts (dgv2_conv_weight_bank_ex; any runtime scale already folded in);
  * no bias, no activation.  DGV2_BF16, C % 32 == 0, O % 32 == 0, contraction length (C forward, O data gradient) <= 512,
- * 16-byte aligned pointers; DGV2_ENOTSUP otherwise: callers then run dgv2_conv_taps on the same operands.
+ * 16-byte aligned pointers; DGV2_ENOTSUP otherwise: callers then run dgv2_conv_direct_fwd / _dgrad on the same operands.
  * replaces: ops.Conv2d forward / data gradient (gans/models/ops/common.py:187-210) of ResidualBlock.skip behind its
  *   decimating blur (gans/models/dusty_v2.py:337-345). */
 int dgv2_conv1x1_fwd(void* y, const void* x, const void* wf, int B, int P, int C, int O, const void* resid, int dtype,
@@ -975,14 +961,13 @@ int dgv2_fp8_quant_weights(void* const* w8, const void* const* src, const int* O
 /* y (bf16) = x (e4m3) * scale for n elements, n % 16 == 0: the saved e4m3 activations as the bf16 operand of the
  * weight-gradient stream (dgv2_conv_wgrad_stream_pl). */
 int dgv2_fp8_dequant(void* y, const void* x, int64_t n, float scale, void* stream);
-/* dgv2_conv_taps (single class, no extras, overwrite) on e4m3 operands x8 [B,Hin,Win,Cin], w8 [O,wtaps,Cin]:
+/* dgv2_conv_direct_fwd on e4m3 operands x8 [B,H,W,Cin], w8 [O,k*k,Cin] (same shapes, padding and epilogue; y / resid bf16):
  *   y (bf16) = act( acc * acc_scale[0] + resid + bias ) * scale,  acc_scale a DEVICE scalar (dgv2_fp8_quant_weights).
- * Cin % 64 == 0, O >= 64; DGV2_ENOTSUP otherwise.  replaces: ops.Conv2d forward (gans/models/ops/common.py:187-210) of
- * ResidualBlock.conv2 / .skip (gans/models/dusty_v2.py:331-345). */
-int dgv2_conv_taps_fp8(void* y, const void* x8, const void* w8, const float* acc_scale, int B, int Hin, int Win, int Cin,
-                       int Hg, int Wg, int O, int Hy, int Wy, int in_stride, int ioff_h, int ioff_w, int ntaps, int wtaps,
-                       const int* taps_host, int ring, const float* bias, const void* resid, int act, float alpha,
-                       float scale, void* stream);
+ * Cin % 64 == 0, O >= 64; DGV2_ENOTSUP otherwise (callers then run the bf16 conv).  replaces: ops.Conv2d forward
+ * (gans/models/ops/common.py:187-210) of ResidualBlock.conv2 / .skip (gans/models/dusty_v2.py:331-345). */
+int dgv2_conv_direct_fwd_fp8(void* y, const void* x8, const void* w8, const float* acc_scale, int B, int H, int W, int Cin,
+                             int O, int k, int stride, const float* bias, const void* resid, int act, float alpha,
+                             float scale, void* stream);
 
 /* Grouped small Linear layers in fp32 on the matrix cores (glin.hip): L <= 24 layers that share the batch B and the
  * input width K in ONE launch, the layers' parameter addresses as HOST arrays (they travel by value in the kernel

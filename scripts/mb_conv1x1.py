@@ -1,5 +1,5 @@
 """The residual blocks' 1x1 skip conv at the benchmark's eight shapes (four blocks, G body B = 64 and D body 2B = 128):
-forward (+ residual) and data gradient, the direct engine (conv_pipe_kernel via dgv2_conv_taps) against conv1x1.hip's
+forward (+ residual) and data gradient, the direct engine (conv_pipe_kernel via dgv2_conv_direct_fwd / _dgrad) against conv1x1.hip's
 streaming GEMM in the same process.  us per launch, GB/s against the HBM floor's byte count (operand read + residual
 read + result written, bf16) and the fraction of the 6.3 TB/s a float4 copy reaches.
 

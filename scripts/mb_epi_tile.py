@@ -14,7 +14,5 @@ for dt in (torch.float32, torch.bfloat16):
         wt = torch.randn(512, 9, 512, device="cuda", dtype=dt)
         fl = 2.0 * B * H * 32 * x.shape[3] * 512 * 9
         t1 = bench._time_launches(lambda: native._conv_fwd_raw(x, w, g), 10)
-        gx = torch.empty(B, H, 32, 512, device="cuda", dtype=dt)
-        taps = [(1 - ky, 1 - kx, ky * 3 + kx) for ky in range(3) for kx in range(3)]
-        t2 = bench._time_launches(lambda: native._conv_taps(gx, gy, wt, H, 32, 1, (0, 0), 1, (0, 0), taps, True), 10)
-        print(f"{dt} B={B} H={H}: fwd {t1*1e6:7.1f} us ({fl/t1/1e12:5.0f} TF/s)  dgrad-like 512->512 {t2*1e6:7.1f} us")
+        t2 = bench._time_launches(lambda: native._conv_dgrad_direct(gy, wt, g, (B, H, 32, 512)), 10)
+        print(f"{dt} B={B} H={H}: fwd {t1*1e6:7.1f} us ({fl/t1/1e12:5.0f} TF/s)  dgrad 512<-512 {t2*1e6:7.1f} us")

@@ -37,6 +37,14 @@ def ada_from_cfg(cfg, p=0.6, device="cpu"):
     return AdaptiveAugment(p_init=p, p_target=0.6, kimg=500, **cfg.training.augment.policy).to(device)
 
 
+def conv_oracle(x, w, stride, pad, ring):
+    """ops.Conv2d (common.py:187-210) on NCHW operands of any dtype: the oracle's padding, then F.conv2d."""
+    from oracle import ops as o
+    if pad:
+        x = o.pad_ring(x, (pad,) * 4, ring)
+    return torch.nn.functional.conv2d(x, w, None, stride)
+
+
 # ---------------------------------------------------------------------------- whole-iteration fixture
 def trainer_fixture_state(d, tag):
     """Initial reference-layout state dicts of tests/golden/trainer_small.npz (weights by recipe, PE buffers and

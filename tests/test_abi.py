@@ -10,10 +10,12 @@ import pytest
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "dgv2.h")
-# forwarding entries retired at ABI 56: each only re-called a wider entry with neutral arguments
+# forwarding entries retired at ABI 56: each only re-called a wider entry with neutral arguments;
+# the direct conv engine's tap-list entries retired at ABI 59 (section 33): dgv2_conv_direct_fwd / _fwd_fp8 / _dgrad
 RETIRED = ("dgv2_bias_act_bwd", "dgv2_bmm_nn", "dgv2_bmm_nn_cat", "dgv2_modconv_pe_fwd", "dgv2_resample_tab",
            "dgv2_resample_tab_add", "dgv2_mbstd_cat_fwd", "dgv2_mbstd_cat_bwd", "dgv2_bmm_tn_stream", "dgv2_bmm_tn_stream_x",
-           "dgv2_conv_wgrad_stream", "dgv2_stem_bwd", "dgv2_conv_weight_bank")
+           "dgv2_conv_wgrad_stream", "dgv2_stem_bwd", "dgv2_conv_weight_bank",
+           "dgv2_conv_taps", "dgv2_conv_taps_ex", "dgv2_conv_taps_ld", "dgv2_conv_taps_fp8")
 
 
 def parse_header():

@@ -88,7 +88,7 @@ CONV_CASES = [  # B, H, W, C, O, k, stride
 
 @pytest.mark.parametrize("B,H,W,C,O,k,stride", CONV_CASES)
 def test_e4m3_conv_is_bit_exact_on_small_integers(nat, B, H, W, C, O, k, stride):
-    """dgv2_conv_taps_fp8 against a float64 ring conv on integer data small enough that every product, partial sum
+    """dgv2_conv_direct_fwd_fp8 against a float64 ring conv on integer data small enough that every product, partial sum
     and the scaled result is exact: pins which channel of a 64-byte K-chunk each lane byte of both operands stands
     for, in every launch variant (reference: ops.Conv2d, gans/models/ops/common.py:187-210, ring padding :10-24)."""
     from gans.models.ops.native import ConvGeom

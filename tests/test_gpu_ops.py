@@ -1061,10 +1061,7 @@ CONVS = [  # B, H, W, C, O, k, stride, pad, ring
 ]
 
 
-def _conv_oracle(x, w, stride, pad, ring):
-    if pad:
-        x = o.pad_ring(x, (pad,) * 4, ring)
-    return torch.nn.functional.conv2d(x, w, None, stride)
+from helpers import conv_oracle as _conv_oracle   # noqa: E402  (shared with test_gpu_conv_direct.py)
 
 
 @pytest.mark.parametrize("cfg", CONVS)
@@ -1216,7 +1213,7 @@ def test_conv_x3_is_fp32_equivalent(nat, B, H, W, C, O):
     """conv_x3.hip (dgv2_conv3x3_x3_fwd / _dgrad: the fp32 3x3 ring conv of the discriminator's fp32 epilogue,
     dusty_v2.py:376-379 under :394-395, on the bf16 matrix cores -- operands as three bf16 planes, six products per multiply)
     against float64 on data with a wide dynamic range, the error per element relative to sum |x||w|: not above what
-    the exact-fp32 MFMA kernel (dgv2_conv_taps, v_mfma_f32_16x16x4_f32) leaves on the same operands, and bit-exact on
+    the exact-fp32 MFMA kernel (dgv2_conv_direct_fwd, v_mfma_f32_16x16x4_f32) leaves on the same operands, and bit-exact on
     small integers.  The epilogue's own shape (513 -> 512 on 4 x 32: a 17th chunk with one live channel, the gradient of
     that channel from the exact-fp32 tail kernel), an odd tile count, two rows of tiles, ragged H, three tile columns;
     bias + leaky ReLU + gain in the forward's epilogue, the sibling gradient in the data gradient's."""
@@ -1592,7 +1589,7 @@ def test_mod_prep_per_layer_matches_reference_vectors(nat, g_ops, tag, demod, bi
 
 @pytest.mark.parametrize("B,H,W", [(2, 64, 512), (3, 16, 64), (1, 24, 32)])
 def test_conv_strip_kernel_forward_and_data_gradient(nat, B, H, W):
-    """conv_strip.hip through dgv2_conv_taps / dgv2_conv_taps_ex (bf16, 32 -> 32 channels, 3x3, ring): forward with the
+    """conv_strip.hip through dgv2_conv_direct_fwd / _dgrad (bf16, 32 -> 32 channels, 3x3, ring): forward with the
     fused bias + leaky ReLU epilogue, and the stride-1 data gradient with the replicate-row border terms and the fused
     residual, against float64 F.conv2d on the ring-padded input (ops.Conv2d, common.py:187-210) and its autograd.
     Integer-valued operands make the bf16 MFMA results exact; random operands use the bf16 tolerance.  The generic
@@ -1850,7 +1847,7 @@ def test_fused_nsgan_loss_matches_ganloss(nat):
 def test_conv_data_gradient_in_channel_ranges(nat, dtype, C):
     """The stride-1 3x3 data gradient of a conv whose input channel count sits just past a multiple of the 64-channel
     slab (the discriminator epilogue's 513 inputs padded to 528 / 544) runs as full slabs + tail through
-    dgv2_conv_taps_ld: against the float64 autograd of F.conv2d on the ring-padded input, with and without residual."""
+    dgv2_conv_direct_dgrad: against the float64 autograd of F.conv2d on the ring-padded input, with and without residual."""
     g = torch.Generator().manual_seed(C)
     B, H, W, O = 3, 4, 32, 64
     geom = nat.ConvGeom(3, 3, 1, 1, True)

@@ -71,7 +71,7 @@ def test_public_surface():
     native = importlib.import_module(NATIVE)
     with open(os.path.join(GOLDEN, "native_public_names.txt")) as f:
         names = f.read().split()
-    assert len(names) >= 116
+    assert len(names) >= 115     # (116 before ABI 59 retired _conv_taps with the tap-list entries)
     mods = {m: _submodule(m) for m in SUBMODULES}
     for name in names:
         assert hasattr(native, name), f"native.{name} no longer resolves"
