@@ -37,6 +37,9 @@ $(BUILD)/knn.o: HIPFLAGS += -fno-slp-vectorize
 # instantiation may fuse a multiply into an add that another leaves alone
 $(BUILD)/segloss.o: HIPFLAGS += -ffp-contract=off
 
+# sgd.hip promises the same bits from its 16-byte and element-wise paths (its fused multiply-adds are written out)
+$(BUILD)/sgd.o: HIPFLAGS += -ffp-contract=off
+
 $(LIB): $(OBJ)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ)

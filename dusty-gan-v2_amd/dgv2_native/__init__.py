@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE
 
 F32, BF16 = 0, 1
 F16 = 3   # the dgv2_seg_loss_* entries and dgv2_fire_fwd only
-ABI_VERSION = 59
+ABI_VERSION = 60
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -95,6 +95,10 @@ SIGNATURES = {
     "dgv2_lerp_list": [_c_ptr] * 3 + [_c_int, _c_f32, _c_ptr],
     "dgv2_adam_prep": [_c_ptr, _c_ptr, _c_f32, _c_f32, _c_ptr],
     "dgv2_adam_step": [_c_ptr] * 5 + [_c_int, _c_ptr] + [_c_f32] * 4 + [_c_ptr],
+    # the segmentation models' optimizer tail (csrc/sgd.hip; replaces train_semseg.py:201-212, 278-283, 360-362)
+    "dgv2_sumsq_list": [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr],
+    "dgv2_clip_prep": [_c_ptr, _c_int, _c_f32, _c_ptr, _c_f32, _c_f32, _c_int, _c_ptr, _c_ptr],
+    "dgv2_sgd_step": [_c_ptr] * 4 + [_c_int, _c_ptr] + [_c_f32] * 3 + [_c_ptr],
     "dgv2_pack2d": [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr],
     "dgv2_unpack2d": [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr],
     "dgv2_ema_scalar": [_c_ptr] * 3 + [_c_int] + [_c_f32] * 3 + [_c_int, _c_ptr, _c_int, _c_ptr],
@@ -236,6 +240,7 @@ def int_array(vals):
     return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
 
 
+EINVAL = -1
 ENOTSUP = -3
 
 
@@ -278,6 +283,8 @@ def scratch_elems(entry, *args):
 # status words (include/dgv2.h "Status words"): the library keeps no flag of its own; entries that check a promise of
 # the caller on the values they stage OR a bit into a device int32 the caller owns.  One word per device, owned here.
 # ---------------------------------------------------------------------------------------
+SUMSQ_PARTS = 64   # DGV2_SUMSQ_PARTS: floats per tensor of the caller-owned partials of dgv2_sumsq_list
+SGD_N_MAX = 2147483647 - (1 << 17)   # DGV2_SGD_N_MAX: the longest tensor dgv2_sumsq_list / dgv2_sgd_step take
 STATUS_X_INEXACT, STATUS_FIR_TABLE = 1, 2
 _STATUS_TEXT = {
     STATUS_X_INEXACT: "a launch with an x_exact promise (fp32 conv on conv_x3.hip / its weight gradient: 'these input "

@@ -384,6 +384,42 @@ int dgv2_adam_prep(float* sc, float* step, float b1, float b2, void* stream);
 int dgv2_adam_step(float* const* p, const float* const* g, float* const* m, float* const* v, const int* n,
                    int L, const float* sc, float lr, float b1, float b2, float eps, void* stream);
 
+/* The optimizer tail of the segmentation models' training step over a list of fp32 tensors (HOST arrays of L <= 72
+ * device pointers, by value in the launch, as dgv2_adam_step): torch.optim.SGD with momentum and weight decay
+ * (dampening 0, no Nesterov; train_semseg.py:201-212, lr as the schedule of 360-362 leaves it in the param group) with
+ * GradScaler.unscale_, clip_grad_norm_, GradScaler.step's overflow skip and GradScaler.update (train_semseg.py:278-283)
+ * folded in.  Three entries, no atomics, no host synchronisation, every launch hipGraph-capturable; the gradients are
+ * only read.  The workspace is the CALLER's: DGV2_SUMSQ_PARTS floats per tensor (no _scratch sibling).
+ *
+ * dgv2_sumsq_list: block (x, l) of a (DGV2_SUMSQ_PARTS, L) grid writes partials[l*DGV2_SUMSQ_PARTS + x] = the sum of
+ *   g[l][i]^2 over its share -- the 4-element groups x*256 + t, + 64*256, ... and one tail element -- accumulated in fp32
+ *   in a fixed order (thread chain of fused multiply-adds, wave reduce, block reduce): the bits depend on n[l] alone
+ *   (16-byte loads where g[l] is 16-byte aligned, element loads of the same groups otherwise).
+ * dgv2_clip_prep: one block adds the `count` partials in double in a fixed order (thread t the partials t, t + 256, ...
+ *   in index order, then a fixed tree) and writes sc (fp32 [4]).  scale_state: fp32 [2] = (loss scale, growth tracker),
+ *   or NULL for "no loss scale".  With s = scale (1 when NULL) and norm = sqrt(sum) / s, computed in double:
+ *     sc[0] = norm                                          the unscaled total gradient norm
+ *     sc[1] = min(1, max_norm / (norm + 1e-6)) / s          the factor on every raw gradient (max_norm <= 0: 1 / s)
+ *     sc[2] = 1 when scale_state is given and sum is not finite, else 0
+ *     sc[3] = s                                             the loss scale this step ran under
+ *   and, when scale_state is given, GradScaler.update: on overflow scale *= backoff, tracker = 0; otherwise tracker += 1
+ *   and, when it equals growth_interval, scale *= growth, tracker = 0.  Without a loss scale a non-finite norm goes on
+ *   into the parameters as it does in the reference (a NaN norm gives a NaN factor).
+ * dgv2_sgd_step: where sc[2] != 0 every block returns before touching p or m; else per element
+ *     d = sc[1]*g + weight_decay*p;   m = momentum*m + d;   p -= lr*m
+ *   evaluated in double from the fp32 operands, m and p each rounded to fp32 once (p from the unrounded m)
+ *   (a momentum buffer of zeros reproduces torch's first step buf = d exactly: no first-step flag).  Five fp32 streams
+ *   per element (p, g, m read; p, m written).  momentum == 0: p -= lr*d, m is neither read nor written (m, or any
+ *   m[l], may be NULL).  DGV2_EINVAL, nothing launched (dgv2_sumsq_list and dgv2_sgd_step alike): a NULL pointer, L
+ *   outside [1, 72], an n[l] that is negative or above DGV2_SGD_N_MAX (the kernels index with int). */
+#define DGV2_SUMSQ_PARTS 64
+#define DGV2_SGD_N_MAX (2147483647 - (1 << 17))
+int dgv2_sumsq_list(const float* const* g, const int* n, int L, float* partials, void* stream);
+int dgv2_clip_prep(const float* partials, int count, float max_norm, float* scale_state, float growth, float backoff,
+                   int growth_interval, float* sc, void* stream);
+int dgv2_sgd_step(float* const* p, const float* const* g, float* const* m, const int* n, int L, const float* sc, float lr,
+                  float momentum, float weight_decay, void* stream);
+
 /* Pack / unpack a list of L <= 48 small fp32 matrices (HOST array of device pointers, by value in the launch)
  * into / out of one zero-padded [L, Rmax, Cmax] tensor: the 19 style affines of the generator (EqualLR Linear
  * of every ModConv2d, style.py:30,75) then run as one batched library GEMM forward and two backward. */

@@ -1,0 +1,137 @@
+"""Train a range-image segmentation model on one GPU (reference: train_semseg.py), headless.
+
+    python train_semseg.py --config configs.yaml [--max_steps N] [--batch_size B] [--out_dir DIR] [--no_fused_optimizer]
+    python train_semseg.py --synthetic --max_steps 100          # no data on disk: semseg.datasets.SyntheticFrontal
+
+Every cfg.training.checkpoint.stats steps one JSON line goes to <out_dir>/train_log.jsonl and to stdout: step, mean
+loss and gradient norm since the last line (over the steps where they are finite; non-finite values are written as
+null and the steps skipped for a float16 overflow are counted), lr, loss scale and the per-class IoU of the training predictions (the only
+place the loop reads anything back).  Every cfg.training.checkpoint.test steps the validation scores are logged and
+<out_dir>/models/checkpoint_step-XXXXXXXXXX.pth is written.  Nothing is fetched from anywhere."""
+import argparse
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+for _p in (ROOT, os.path.join(ROOT, "dusty-gan-v2_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from semseg.config import default_config, load_config  # noqa: E402
+from semseg.datasets import GTALiDAR, GTALiDAR_GAN, KITTIRawFrontal, SyntheticFrontal  # noqa: E402
+from semseg.metrics import counts_from_confusion  # noqa: E402
+from semseg.trainer import Trainer  # noqa: E402
+from semseg.utils import InfiniteSampler  # noqa: E402
+
+RAYDROP_MAP = "data/avg_raydrop/kitti_raw_frontal.npy"
+
+
+def build_datasets(cfg, synthetic):
+    """(train, val) for cfg.dataset.name (the reference's table, train_semseg.py:80-106), or the synthetic pair."""
+    shape, flip = tuple(cfg.dataset.shape), cfg.dataset.random_flip
+    if synthetic:
+        n = int(cfg.dataset.num_classes)
+        return (SyntheticFrontal(256, shape, n, seed=cfg.random_seed), SyntheticFrontal(32, shape, n, seed=cfg.random_seed + 1))
+    name = cfg.dataset.name
+    val = KITTIRawFrontal(split="val", shape=shape)
+    if name == "kitti_raw_frontal":
+        return KITTIRawFrontal(split="train", shape=shape, flip=flip), val
+    if name in ("gta_lidar", "gta_lidar_w_uniform_noise"):
+        dropout_map = np.load(RAYDROP_MAP)
+        if name == "gta_lidar_w_uniform_noise":
+            dropout_map.fill(dropout_map.mean())
+        return GTALiDAR(shape=shape, flip=flip, raydrop_p=dropout_map), val
+    if name == "gta_lidar_wo_noise":
+        return GTALiDAR(shape=shape, flip=flip, raydrop_p=None), val
+    gan_dirs = {"gta_lidar_w_gan_noise_dustyv1": "GTAV_noise_v1", "gta_lidar_w_gan_noise_dustyv2": "GTAV_noise_v2"}
+    if name in gan_dirs:
+        return GTALiDAR_GAN(shape=shape, flip=flip, gan_dir=gan_dirs[name]), val
+    raise ValueError(name)
+
+
+def finite_or_none(x):
+    """A float for the JSON log: non-finite values (the gradient norm of a step skipped for an overflow) become null."""
+    x = float(x)
+    return x if math.isfinite(x) else None
+
+
+def mean_finite(ts):
+    """Mean over the finite entries of a list of 0-dim device tensors (one readback), None where there is none."""
+    v = torch.stack(ts).double()
+    ok = torch.isfinite(v)
+    return finite_or_none(v[ok].mean()) if bool(ok.any()) else None
+
+
+def iou_list(conf, eps=1e-12):
+    tp, fp, fn = (t.double().cpu() for t in counts_from_confusion(conf))
+    return (tp / (tp + fp + fn + eps)).tolist()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--config", type=str, default=None)
+    ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--max_steps", type=int, default=None)
+    ap.add_argument("--batch_size", type=int, default=None)
+    ap.add_argument("--out_dir", type=str, default=None)
+    ap.add_argument("--no_fused_optimizer", action="store_true")
+    args = ap.parse_args(argv)
+    if args.config is None and not args.synthetic:
+        ap.error("--config or --synthetic is required")
+
+    cfg = load_config(args.config) if args.config else default_config()
+    if args.max_steps is not None:
+        cfg.training.max_steps = args.max_steps
+    if args.batch_size is not None:
+        cfg.training.batch_size = args.batch_size
+    out_dir = args.out_dir or os.path.join("logs", "semseg", cfg.dataset.name, cfg.arch.name)
+    os.makedirs(os.path.join(out_dir, "models"), exist_ok=True)
+
+    torch.manual_seed(cfg.random_seed)
+    np.random.seed(cfg.random_seed)
+    device = torch.device("cuda", 0)
+    train_set, val_set = build_datasets(cfg, args.synthetic)
+    workers = int(cfg.training.get("num_workers", 0))
+    loader = torch.utils.data.DataLoader(train_set, batch_size=cfg.training.batch_size, num_workers=workers,
+                                         sampler=InfiniteSampler(train_set, seed=cfg.random_seed), drop_last=True)
+    val_loader = torch.utils.data.DataLoader(val_set, batch_size=cfg.training.batch_size, num_workers=workers)
+    trainer = Trainer(cfg, device, fused_optimizer=not args.no_fused_optimizer,
+                      pretrained_weights=not args.synthetic)
+
+    ck = cfg.training.checkpoint
+    log_path = os.path.join(out_dir, "train_log.jsonl")
+    losses, norms = [], []
+    batches = iter(loader)
+    with open(log_path, "a") as log:
+        def emit(row):
+            line = json.dumps(row, allow_nan=False)
+            log.write(line + "\n")
+            log.flush()
+            print(line, flush=True)
+
+        for step in range(1, int(cfg.training.max_steps) + 1):
+            lr = trainer.optimizer.param_groups[0]["lr"]
+            out = trainer.step(next(batches))
+            losses.append(out["loss"])
+            norms.append(out["grad_norm"])
+            last = step == int(cfg.training.max_steps)
+            if step % int(ck.stats) == 0 or last:
+                emit({"step": step, "loss": mean_finite(losses), "lr": lr, "grad_norm": mean_finite(norms),
+                      "skipped_steps": int((~torch.isfinite(torch.stack(norms))).sum()), "loss_scale": trainer.loss_scale(),
+                      "iou": iou_list(trainer.conf_train), "classes": list(train_set.class_list)})
+                trainer.reset_conf()
+                losses, norms = [], []
+            if step % int(ck.test) == 0 or last:
+                val = trainer.validate(val_loader)
+                emit({"step": step, "val_iou": [finite_or_none(v) for v in val["iou"]], "val_mean_iou": finite_or_none(val["mean_iou"])})
+                torch.save(trainer.state_dict(), os.path.join(out_dir, "models", f"checkpoint_step-{step:010d}.pth"))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
