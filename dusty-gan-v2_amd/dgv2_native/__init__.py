@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libdgv2.so")
 
 F32, BF16 = 0, 1
-F16 = 3   # the dgv2_seg_loss_* entries and dgv2_fire_fwd only
+F16 = 3   # the dgv2_seg_loss_* entries, dgv2_fire_fwd and dgv2_cam_fwd only
 ABI_VERSION = 60
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -176,6 +176,7 @@ SIGNATURES = {
     "dgv2_seg_loss_forward": [_c_ptr] * 5 + [_c_i64] + [_c_ptr] * 4 + [_c_int] * 4 + [_c_f32, _c_int, _c_ptr],
     "dgv2_seg_loss_backward": [_c_ptr] * 7 + [_c_int] * 4 + [_c_f32, _c_int, _c_int, _c_ptr],
     "dgv2_fire_fwd": [_c_ptr] * 23 + [_c_f32] * 3 + [_c_int] * 9 + [_c_ptr],
+    "dgv2_cam_fwd": [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr],
 }
 
 

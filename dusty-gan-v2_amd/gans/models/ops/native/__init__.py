@@ -14,7 +14,7 @@ and ends in a literal __all__; a module-level switch (a name read from os.enviro
 scripts read and set it as <module>.<FLAG>.  Everything in a submodule's __all__ is also reachable as native.<name>.
 """
 import dgv2_native as N  # noqa: F401  (native.N: the ctypes binding)
-from . import (act_resample, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, loss, modgemm, modlayer,  # noqa: F401
+from . import (act_resample, cam, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, loss, modgemm, modlayer,  # noqa: F401
                modup, optim, rng, second_order, segloss, sgd, stem_tail_ada)
 from .act_resample import *  # noqa: F401,F403
 from .fourier import *  # noqa: F401,F403
@@ -36,4 +36,5 @@ from .crf import *  # noqa: F401,F403
 from .knn import *  # noqa: F401,F403
 from .segloss import *  # noqa: F401,F403
 from .fire import *  # noqa: F401,F403
+from .cam import *  # noqa: F401,F403
 from .sgd import *  # noqa: F401,F403

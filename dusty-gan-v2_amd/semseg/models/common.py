@@ -1,14 +1,18 @@
 """Building blocks of the SqueezeSeg trunks (reference: semseg/models/common.py): weight initialisers, the conv /
 norm / activation sequences whose state-dict layout the published checkpoints fix, and the routing of an
-evaluation-mode Fire module onto the one-launch native kernel (gans.models.ops.native.fire).
+evaluation-mode Fire module and of an evaluation-mode context-aggregation module onto their one-launch native kernels
+(gans.models.ops.native.fire; gans.models.ops.native.cam, section 35).
 """
 import torch
 from torch import nn
 
+from gans.models.ops.native import cam as _cam
 from gans.models.ops.native import fire as _fire
 
 # False forces the composition of library ops in every Fire module (tests, A/B timing); read at every call
 FIRE_NATIVE = True
+# the same switch for the context-aggregation modules; DESIGN.md section 35 has the measurement behind its default
+CAM_NATIVE = True
 
 _INPUT_CHANNELS = {"xyz": 3, "depth": 1, "reflectance": 1, "mask": 1}
 
@@ -148,3 +152,31 @@ def fire_forward(fire, x, skip=None):
     if fire_uses_native(fire, x):
         return fire_native(fire, x, skip)
     return fire_composition(fire, x, skip)
+
+
+def cam_uses_native(cam, x):
+    """The routing rule of the context-aggregation module, Fire's rule: a CUDA input, eval(), grad mode off, the
+    switch on, and a configuration the kernel covers."""
+    if not (CAM_NATIVE and x.is_cuda and not cam.training and not torch.is_grad_enabled()):
+        return False
+    squeeze, excite = cam.attn[1], cam.attn[3]
+    if squeeze.bias is None or excite.bias is None:
+        return False
+    return x.ndim == 4 and _cam.cam_supported(squeeze.in_channels, squeeze.out_channels, x.dtype)
+
+
+def cam_native(cam, x):
+    """One native launch for a context-aggregation module.  Reads the module's current parameters."""
+    squeeze, excite = cam.attn[1], cam.attn[3]
+    return _cam.cam_forward(x, squeeze.weight, squeeze.bias, excite.weight, excite.bias)
+
+
+def cam_composition(cam, x):
+    """The same module as library tensor ops, differentiable: the training path and the native path's yardstick."""
+    return x * cam.attn(x)
+
+
+def cam_forward(cam, x):
+    if cam_uses_native(cam, x):
+        return cam_native(cam, x)
+    return cam_composition(cam, x)

@@ -1,7 +1,7 @@
 """SqueezeSegV2 trunk for range images (reference: semseg/models/squeezeseg_v2.py): V1's layout with a batch norm
 after every ReLU and three context-aggregation modules in the encoder.  Module tree and state-dict layout are the
 reference's, so a published checkpoint's ckpt["model"] loads with strict=True; in eval() with grad mode off every
-Fire module is one native launch.  The SqueezeNet initialisation is read from a local file only."""
+Fire module and every context-aggregation module is one native launch.  The SqueezeNet initialisation is read from a local file only."""
 from functools import partial
 from pathlib import Path
 
@@ -9,8 +9,8 @@ import joblib
 import torch
 from torch import nn
 
-from .common import (ConvReLUNorm, DeconvReLU, Head, fire_forward, init_weights_trunc_normal, init_weights_xavier,
-                     setup_in_ch)
+from .common import (ConvReLUNorm, DeconvReLU, Head, cam_forward, fire_forward, init_weights_trunc_normal,
+                     init_weights_xavier, setup_in_ch)
 from .crf_as_rnn import CRFRNN
 
 # encoder Fire modules -> their names in the SqueezeNet v1.1 pickle
@@ -20,7 +20,8 @@ SQUEEZENET_FILE = Path(__file__).parent / "pretrained" / "squeezenet_v1.1.pkl"
 
 
 class CAM(nn.Module):
-    """Context aggregation module: the input gated by a squeeze-and-excite map of its 7x7 max-pool."""
+    """Context aggregation module: the input gated by a squeeze-and-excite map of its 7x7 max-pool.  In eval() with
+    grad mode off it is one native launch (common.cam_forward has the rule)."""
 
     def __init__(self, ch, reduction=16):
         super().__init__()
@@ -28,7 +29,7 @@ class CAM(nn.Module):
                                   nn.Conv2d(ch // reduction, ch, 1, 1, 0), nn.Sigmoid())
 
     def forward(self, x):
-        return x * self.attn(x)
+        return cam_forward(self, x)
 
 
 class Fire(nn.Module):

@@ -29,7 +29,7 @@ extern "C" {
 #define DGV2_F32 0
 #define DGV2_BF16 1
 #define DGV2_FP8 2 /* OCP e4m3fn bytes; only where an entry says so (the *_fp8 / *_q8 entries) */
-#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits; dgv2_fire_fwd) */
+#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits; dgv2_fire_fwd; dgv2_cam_fwd) */
 #define DGV2_EINVAL (-1)
 #define DGV2_ENOTSUP (-3) /* valid request that this build's kernels do not cover: use the documented fallback */
 
@@ -1245,6 +1245,31 @@ int dgv2_fire_fwd(void* y, const void* x, const void* skip, const float* w_s, co
                   const float* var_1, const float* w_3, const float* b_3, const float* g_3, const float* beta_3,
                   const float* mean_3, const float* var_3, float eps_s, float eps_1, float eps_3, int B, int Cin,
                   int Cs, int E1, int E3, int H, int W, int up, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Context aggregation module (CAM) of SqueezeSegV2, evaluation mode (cam.hip; semseg/models/squeezeseg_v2.py here)
+ * replaces: the reference's context-aggregation class, semseg/models/squeezeseg_v2.py:20-36 -- MaxPool2d(7, 1, 3),
+ *   Conv2d(C, Cr, 1), ReLU, Conv2d(Cr, C, 1), Sigmoid and the multiply: six launches -- with ONE launch.
+ * x and y [B,C,H,W] are contiguous NCHW of one `dtype` (DGV2_F32, DGV2_BF16 or DGV2_F16) and do not overlap (a
+ * block reads the halo of pixels that another block writes).  Every parameter is float32
+ * in the layout of its torch module: w1 [Cr,C,1,1], b1 [Cr], w2 [C,Cr,1,1], b2 [C].  Per sample and pixel (h, w):
+ *   m[c] = max of x[c][h'][w'] over |h' - h| <= 3, |w' - w| <= 3 INSIDE the image: the padding is -inf, not 0, so a
+ *          window never sees a value that is not in x (max is exact in every dtype)
+ *   a[j] = relu(t_C + b1[j]),  t_0 = 0, t_{c+1} = fmaf(w1[j][c], m[c], t_c)        c = 0 .. C-1 in increasing order
+ *   s[c] = u_Cr + b2[c],       u_0 = 0, u_{j+1} = fmaf(w2[c][j], a[j], u_j)        j = 0 .. Cr-1 in increasing order
+ *   g[c] = 1 / (1 + expf(-s[c]))                                                   (correctly rounded divide)
+ *   y[c] = x[c] * g[c]                                                             rounded once to `dtype`
+ * all in float32: the parameters are used as they are, m is converted exactly, a and g are never rounded to the
+ * activations' dtype.  m reaches LDS and registers only (a separable row-then-column maximum over a haloed 8 x 32
+ * tile, eight channels at a time; the parameters are staged once per block in LDS); no atomics, no workspace; each
+ * output is one fixed-order chain of its own pixel, so its bits depend neither on the grid nor on the batch.  A NaN
+ * in x is dropped by the maximum where torch's pool propagates it.
+ * Range: C a multiple of 16, 16 <= C <= 128; 1 <= Cr <= 8; B, H, W >= 1; C*H*W <= 2^31 - 1 (offsets inside a sample are
+ * 32-bit).  DGV2_EINVAL, nothing launched and y untouched: outside that range, another dtype, a null pointer, more than
+ * 2^31 - 1 blocks.
+ * ------------------------------------------------------------------------- */
+int dgv2_cam_fwd(void* y, const void* x, const float* w1, const float* b1, const float* w2, const float* b2, int B,
+                 int C, int Cr, int H, int W, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
