@@ -381,6 +381,77 @@ __global__ __launch_bounds__(EMD_NT) void emd_approxmatch_kernel(float* __restri
   }
 }
 
+// The third sweep of a level with the match cost folded in (no match matrix): w_kl = e_kl ratioR_l ratioL_k and the
+// remainL update exactly as SweepM forms them; where SweepM stores w_kl into match[l, k], this adds w_kl |x1_k - x2_l|
+// to the lane's running cost.  Same loop nest as emd_sweep (own passes outer, l ascending), which hands its body
+// e_kl ratioR_l but not the squared distance the square root needs.
+__device__ __forceinline__ float emd_sweep_cost(float4* tile, const float* __restrict__ own, int n_own,
+                                                const float* __restrict__ other, const float* ratioR, int n_other,
+                                                float level, const float* ratioL, float* remainL, float cost) {
+  const int tid = threadIdx.x;
+  for (int k0 = 0; k0 < n_own; k0 += EMD_NT) {
+    const int k = k0 + tid;
+    float x = 0.f, y = 0.f, z = 0.f, rl = 0.f, acc = 0.f;
+    if (k < n_own) x = own[3 * k], y = own[3 * k + 1], z = own[3 * k + 2], rl = ratioL[k];
+    for (int l0 = 0; l0 < n_other; l0 += EMD_NT) {
+      const int cnt = min(EMD_NT, n_other - l0);
+      __syncthreads();
+      if (tid < cnt) tile[tid] = make_float4(other[3 * (l0 + tid)], other[3 * (l0 + tid) + 1], other[3 * (l0 + tid) + 2], ratioR[l0 + tid]);
+      __syncthreads();
+      if (k < n_own) {
+#pragma unroll 4
+        for (int l = 0; l < cnt; ++l) {
+          const float4 t = tile[l];
+          const float dx = t.x - x, dy = t.y - y, dz = t.z - z;
+          const float d2 = dx * dx + dy * dy + dz * dz;
+          float w = __expf(level * d2) * t.w;
+          w *= rl;
+          acc += w;
+          cost += w * __builtin_amdgcn_sqrtf(d2);   // v_sqrt_f32, 1 ulp: sqrtf's correctly rounded sequence is 17 more VALU ops a pair
+        }
+      }
+    }
+    if (k < n_own) remainL[k] = fmaxf(0.0f, remainL[k] - acc);
+  }
+  __syncthreads();
+  return cost;
+}
+
+// cost[i, j] = sum_levels sum_kl w_kl |x1_k - x2_l| of cloud i of xyz1 against cloud j of xyz2: what matchcost(approxmatch)
+// returns for that pair, without the match matrix (earth_mover_distance.cu:3-226 for one pair; the (row, chunk) loop of
+// cov_mmd_1nna.py:16-40 is the grid).  One workgroup per pair, grid (B2, B1); remainL / remainR / ratioL / ratioR
+// (2 (n + m) floats) live in LDS beside the 16 KB tile; the first two sweeps of a level are emd_sweep with SweepL /
+// SweepR, so the matching state follows the arithmetic of emd_approxmatch_kernel.
+// Cost chain of a lane: levels outer (j = 7 .. -1), then its own points k = tid, tid + 1024, ..., then l ascending:
+// 9 ceil(n / 1024) m adds; then block_sum's fixed tree (6 butterfly steps, then 16 wave partials in order): 22 adds.
+__global__ __launch_bounds__(EMD_NT) void emd_pairwise_cost_kernel(float* __restrict__ cost,
+                                                                   const float* __restrict__ xyz1,
+                                                                   const float* __restrict__ xyz2, int n, int m) {
+  __shared__ float4 tile[EMD_NT];
+  __shared__ float state[2 * DGV2_EMD_PAIR_MAX_POINTS];
+  __shared__ float red[16];
+  const int bi = blockIdx.y, bj = blockIdx.x, tid = threadIdx.x;
+  const float* p1 = xyz1 + (size_t)bi * n * 3;
+  const float* p2 = xyz2 + (size_t)bj * m * 3;
+  float* remainL = state;
+  float* remainR = remainL + n;
+  float* ratioL = remainR + m;
+  float* ratioR = ratioL + n;
+  const float multiL = n >= m ? 1.f : (float)(m / n), multiR = n >= m ? (float)(n / m) : 1.f;   // integer quotients
+  for (int k = tid; k < n; k += EMD_NT) remainL[k] = multiL;
+  for (int l = tid; l < m; l += EMD_NT) remainR[l] = multiR;
+  __syncthreads();
+  float acc = 0.f;
+  for (int j = 7; j > -2; --j) {
+    const float level = -powf(4.0f, (float)j);
+    emd_sweep(tile, p1, n, p2, remainR, m, level, SweepL{ratioL, remainL, 0.f});
+    emd_sweep(tile, p2, m, p1, ratioL, n, level, SweepR{ratioR, remainR, 0.f});
+    acc = emd_sweep_cost(tile, p1, n, p2, ratioR, m, level, ratioL, remainL, acc);
+  }
+  acc = block_sum(acc, red);
+  if (tid == 0) cost[(size_t)bi * gridDim.x + bj] = acc;
+}
+
 // cost[b] = sum_{k,l} match[l, k] |x1_k - x2_l|     (:177-226); grid (chunks of l, B), atomics into a zeroed cost
 __global__ __launch_bounds__(256) void emd_matchcost_kernel(float* __restrict__ cost, const float* __restrict__ match,
                                                             const float* __restrict__ xyz1,
@@ -582,6 +653,15 @@ extern "C" int dgv2_emd_matchcost(float* cost, const float* match, const float* 
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(cost, 0, (size_t)B * sizeof(float), st) != hipSuccess) return (int)hipErrorUnknown;
   emd_matchcost_kernel<<<dim3(min(m, 32), B), 256, 0, st>>>(cost, match, xyz1, xyz2, n, m);
+  DGV2_RETURN_LAST();
+}
+
+extern "C" int dgv2_emd_pairwise_cost(float* cost, const float* xyz1, const float* xyz2, int B1, int B2, int n, int m,
+                                      void* stream) {
+  if (!cost || !xyz1 || !xyz2 || B1 < 0 || B2 < 0 || n <= 0 || m <= 0 || B1 > 65535) return DGV2_EINVAL;
+  if ((int64_t)n + m > DGV2_EMD_PAIR_MAX_POINTS) return DGV2_ENOTSUP;
+  if (B1 == 0 || B2 == 0) return 0;
+  emd_pairwise_cost_kernel<<<dim3(B2, B1), EMD_NT, 0, (hipStream_t)stream>>>(cost, xyz1, xyz2, n, m);
   DGV2_RETURN_LAST();
 }
 

@@ -65,6 +65,7 @@ SIGNATURES = {
     "dgv2_emd_approxmatch": [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr],
     "dgv2_emd_matchcost": [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr],
     "dgv2_emd_matchcost_grad": [_c_ptr] * 5 + [_c_int] * 3 + [_c_ptr],
+    "dgv2_emd_pairwise_cost": [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr],
     "dgv2_nsgan_loss": [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_f32, _c_ptr, _c_ptr, _c_ptr],
     "dgv2_modconv_pe_dgrad_actbwd_scratch": [_c_ptr] + [_c_int] * 4,
     "dgv2_modconv_pe_dgrad_actbwd": [_c_ptr, _c_ptr, _c_ptr, _c_i64] + [_c_ptr] * 4 + [_c_f32, _c_f32] + [_c_int] * 4 + [_c_ptr],

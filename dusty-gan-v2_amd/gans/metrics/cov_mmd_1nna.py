@@ -8,6 +8,7 @@ plumbing: the reference sends the EMD batch through torch.nn.parallel.data_paral
 import torch
 
 from .distance import chamfer_distance, density_aware_chamfer_distance, earth_mover_distance
+from .distance.emd.earth_mover_distance import pairwise_emd_cost
 
 
 def compute_emd(pcs_1, pcs_2):
@@ -77,12 +78,26 @@ def _compute_nna(M_rr, M_rg, M_gg, k, sqrt=False):
     return s
 
 
+ENGINES = ("batched", "pairwise")
+
+
+def _distance_matrices(pcs_1, pcs_2, batch_size, metrics, verbose, engine):
+    """_pairwise_distance; with engine="pairwise" the "emd" matrix is one launch of the match-free all-pairs kernel."""
+    if engine == "batched" or "emd" not in metrics:
+        return _pairwise_distance(pcs_1, pcs_2, batch_size, metrics, verbose)
+    out = _pairwise_distance(pcs_1, pcs_2, batch_size, tuple(k for k in metrics if k != "emd"), verbose)
+    out["emd"] = pairwise_emd_cost(pcs_1.contiguous(), pcs_2.contiguous()) / float(pcs_1.size(1))
+    return out
+
+
 @torch.no_grad()
-def compute_cov_mmd_1nna(pcs_gen, pcs_ref, batch_size, metrics=("cd", "emd", "dcd"), verbose=True):
+def compute_cov_mmd_1nna(pcs_gen, pcs_ref, batch_size, metrics=("cd", "emd", "dcd"), verbose=True, engine="batched"):
     assert isinstance(metrics, tuple)
-    M_rr = _pairwise_distance(pcs_ref, pcs_ref, batch_size, metrics, verbose)
-    M_rg = _pairwise_distance(pcs_ref, pcs_gen, batch_size, metrics, verbose)
-    M_gg = _pairwise_distance(pcs_gen, pcs_gen, batch_size, metrics, verbose)
+    if engine not in ENGINES:
+        raise ValueError(f"compute_cov_mmd_1nna: engine must be one of {ENGINES}, got {engine!r}")
+    M_rr = _distance_matrices(pcs_ref, pcs_ref, batch_size, metrics, verbose, engine)
+    M_rg = _distance_matrices(pcs_ref, pcs_gen, batch_size, metrics, verbose, engine)
+    M_gg = _distance_matrices(pcs_gen, pcs_gen, batch_size, metrics, verbose, engine)
     results = {}
     for metric in metrics:
         for k, v in _compute_cov_mmd(M_rg[metric]).items():

@@ -973,6 +973,29 @@ int dgv2_emd_matchcost(float* cost, const float* match, const float* xyz1, const
 int dgv2_emd_matchcost_grad(float* grad1, float* grad2, const float* match, const float* xyz1, const float* xyz2, int B,
                             int n, int m, void* stream);
 
+/* all-pairs approximate-matching EMD cost without the match matrix (the distance matrices of COV / MMD / 1-NNA)
+ * replaces: the (row, chunk) loop of _pairwise_distance over earth_mover_distance for the "emd" metric
+ *   gans/metrics/cov_mmd_1nna.py:16-40, gans/metrics/distance/emd/earth_mover_distance.cu:3-226
+ * xyz1 fp32 [B1, n, 3], xyz2 fp32 [B2, m, 3]; cost fp32 [B1, B2] (written), cost[i, j] = what dgv2_emd_matchcost returns
+ * for dgv2_emd_approxmatch(xyz1[i], xyz2[j]); NOT divided by the point count.
+ * arithmetic, per pair: remainL = multiL, remainR = multiR (the integer quotients max(m / n, 1), max(n / m, 1)); for
+ * level = -4^j, j = 7 .. -1, with e_kl = __expf(level |x1_k - x2_l|^2):
+ *   ratioL_k = remainL_k / (1e-9 + sum_l e_kl remainR_l)
+ *   s_l = remainR_l sum_k e_kl ratioL_k;  ratioR_l = min(remainR_l / (s_l + 1e-9), 1) remainR_l;  remainR_l = max(0, remainR_l - s_l)
+ *   w_kl = e_kl ratioR_l ratioL_k;  cost += w_kl |x1_k - x2_l|;  remainL_k = max(0, remainL_k - sum_l w_kl)
+ * (the state arithmetic is that of dgv2_emd_approxmatch, term for term; |.| is the hardware square root, 1 ulp)
+ * One workgroup of 1024 lanes per pair, grid (B2, B1); the four state arrays (2 (n + m) floats) and a 16 KB tile of the
+ * other cloud live in LDS; no workspace, no memset, no atomics.  A lane's cost chain is in fixed order: levels outer,
+ * then its own points k = lane, lane + 1024, ..., then l ascending (9 ceil(n / 1024) m adds); one fixed-tree block sum
+ * (6 butterfly steps, then the 16 wave partials in order) ends it: the same bits for a pair wherever it sits in the grid.
+ * n, m >= 1 and n + m <= DGV2_EMD_PAIR_MAX_POINTS (state + tile = 48 KB of LDS); B1 <= 65535.  DGV2_ENOTSUP above the
+ * cap (callers fall back to the batched entries above), DGV2_EINVAL for null pointers or a bad shape; nothing is
+ * launched in either case.  No gradient.
+ * ------------------------------------------------------------------------- */
+#define DGV2_EMD_PAIR_MAX_POINTS 4096
+int dgv2_emd_pairwise_cost(float* cost, const float* xyz1, const float* xyz2, int B1, int B2, int n, int m,
+                           void* stream);
+
 /* ---- fp8 (OCP e4m3) operands for the decimating branch convs of the discriminator (BASELINE configs[4]) --------------
  * The two tensors of a ResidualBlock (gans/models/dusty_v2.py:325-345) that exist only as MFMA operands -- the blurred
  * activation in front of the 3x3 stride-2 conv2 and the blur-decimated block input in front of the 1x1 skip conv -- are
