@@ -178,6 +178,8 @@ SIGNATURES = {
     "dgv2_seg_loss_backward": [_c_ptr] * 7 + [_c_int] * 4 + [_c_f32, _c_int, _c_int, _c_ptr],
     "dgv2_fire_fwd": [_c_ptr] * 23 + [_c_f32] * 3 + [_c_int] * 9 + [_c_ptr],
     "dgv2_cam_fwd": [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr],
+    "dgv2_bev_render": [_c_ptr] * 6 + [_c_int] * 4 + [_c_f32, _c_ptr],
+    "dgv2_bilinear_splat": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr],
 }
 
 

@@ -11,6 +11,8 @@ from torch import nn
 
 from gans.geometry import estimate_surface_normal
 from gans.models.ops import native
+from gans.render import render_point_clouds
+from gans.utils import points_to_normal_2d
 
 
 class _CoordType:
@@ -126,6 +128,15 @@ class CoordBridge(nn.Module):
     def depth_to_point_map(self, depth):
         assert depth.dim() == 4
         return self._k(depth, 3)
+
+    def make_birds_eye_view(self, inv_depth, Rt):
+        """inv_depth [B,1,H,W] in [0,1] -> the normal-coloured bird's-eye view [B,3,W,W] under the extrinsics
+        Rt = (R, t) of gans.render.make_Rt (reference: coords.py:187-196): the conversion, normal and splat kernels."""
+        R, t = Rt
+        W = inv_depth.shape[-1]
+        points = self.convert(inv_depth, CoordType.INV_DEPTH_NORM, CoordType.POINT_MAP) / self.max_depth
+        normal = points_to_normal_2d(points, mode="closest")
+        return render_point_clouds(points.flatten(2).transpose(1, 2), normal.flatten(2).transpose(1, 2), size=W, R=R, t=t)
 
     def extra_repr(self):
         return f'H={self.H}, W={self.W}, min_depth={self.min_depth}, max_depth="{self.max_depth}"'

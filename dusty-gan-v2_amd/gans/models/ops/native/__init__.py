@@ -15,7 +15,7 @@ scripts read and set it as <module>.<FLAG>.  Everything in a submodule's __all__
 """
 import dgv2_native as N  # noqa: F401  (native.N: the ctypes binding)
 from . import (act_resample, cam, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, loss, modgemm, modlayer,  # noqa: F401
-               modup, optim, rng, second_order, segloss, sgd, stem_tail_ada)
+               modup, optim, render, rng, second_order, segloss, sgd, stem_tail_ada)
 from .act_resample import *  # noqa: F401,F403
 from .fourier import *  # noqa: F401,F403
 from .glin import *  # noqa: F401,F403
@@ -38,3 +38,4 @@ from .segloss import *  # noqa: F401,F403
 from .fire import *  # noqa: F401,F403
 from .cam import *  # noqa: F401,F403
 from .sgd import *  # noqa: F401,F403
+from .render import *  # noqa: F401,F403

@@ -1,6 +1,6 @@
 """Training-path utilities (reference: gans/utils.py:21-42, 85-105, 238-271) and the visualisation helpers a latent
-walk needs: cycle, colorize, points_to_normal_2d (utils.py:136-138, 167-202).  The rest of the reference file's
-visualisation code (video writers, spectra) is out of scope."""
+walk and the training log need: cycle, colorize, points_to_normal_2d, power_spectrum_2d (utils.py:136-138, 167-209).
+The rest of the reference file's visualisation code (the video writers) is out of scope."""
 import os
 import random
 
@@ -85,6 +85,13 @@ def points_to_normal_2d(points_map, mode="closest", d=2):
     normals = estimate_surface_normal(points_map, d=d, mode=mode).neg_()
     normals[normals != normals] = 0.0
     return tanh_to_sigmoid(normals).clamp_(0.0, 1.0)
+
+
+def power_spectrum_2d(x):
+    """(..., H, W) -> the centred 2-D power spectrum in dB (reference: utils.py:205-209).  A torch.fft composition: it
+    runs once per image log."""
+    spectrum = torch.fft.fftshift(torch.fft.fft2(x, norm="forward"), dim=[-1, -2])
+    return 10 * torch.log10(spectrum.abs() ** 2)
 
 
 class InfiniteSampler(torch.utils.data.Sampler):

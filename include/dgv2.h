@@ -1294,6 +1294,41 @@ int dgv2_fire_fwd(void* y, const void* x, const void* skip, const float* w_s, co
 int dgv2_cam_fwd(void* y, const void* x, const float* w1, const float* b1, const float* w2, const float* b2, int B,
                  int C, int Cr, int H, int W, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Bird's-eye view of a point cloud, and the bilinear splat under it (bev.hip; gans/render.py here)
+ * replaces: render.py:21-127 -- render_point_clouds (kornia's pinhole projection, the mask, the depth weight) and
+ *   bilinear_rasterizer: about 70 tensor-op launches over [B,N,C] temporaries with four float scatter_add_ calls, whose
+ *   sums depend on the arrival order -- with three launches (clear, splat, resolve) whose output bits do not.
+ * dgv2_bev_render: points [B,N,3], colors [B,N,C] (1 <= C <= 4, values in [-1, 1]), R [3,3] or NULL, t [3] or NULL,
+ * out [B,C,size,size], all float32 and contiguous.  Per point, in float32:
+ *   p = (x, y, -z);  p = p . R (row vector times matrix) if R;  p += t if t
+ *   s = 1 / (p_z + 1e-8) if |p_z| > 1e-8 else 1;   u_k = (p_k * s * focal + 0.5) * size, k = x, y   (principal point
+ *       0.5; a point behind the camera projects too, mirrored)
+ *   keep = 0 < u_x < size - 1 and 0 < u_y < size - 1 (strict);  row = size - u_x, col = size - u_y
+ *   d = |p|;  e = expf(-3 d) if d > 1e-8 else 0
+ *   for the four corners (floor(row) + i, floor(col) + j), i, j in {0, 1}, with the bilinear weight b: a corner outside
+ *   [0, size - 1]^2 or with b < 1e-3 is dropped;  num[c] += (e * b) * colors[c] if keep;  den += e * b  (a point that is
+ *   not kept still dilutes its pixels)
+ *   out = num / (den + 1e-8)                                               (in double, rounded once to float)
+ * dgv2_bilinear_splat: the same splat with e = 1, keep = 1, the raster coordinates given (coords [B,N,2] = (row, col))
+ * and no division: out [B,C,H,W] = sum of b * values[c] (values [B,N,C] in [-1, 1]).
+ * Accumulation is in 64-bit integers: each addend is saturated to [-1, 1], scaled by 2^40 (exact for a float), rounded
+ * to an integer and added with an integer atomic.  Integer addition is associative: the output is bit-identical from
+ * run to run and under any permutation of the points.  Only bits below 2^-40 of an addend are lost; N < 2^22 keeps
+ * N * 2^40 < 2^63.
+ * acc: int64, caller-allocated, [B,size,size,C+1] for dgv2_bev_render and [B,H,W,C] for dgv2_bilinear_splat; its
+ * contents on entry do not matter (the entry clears it) and are the scaled sums afterwards.  Its size is this formula,
+ * not a library plan: there is no _scratch sibling.
+ * A coordinate becomes an index only behind a range comparison on the float, so a NaN or huge coordinate drops its point
+ * and never forms an address; non-finite inputs are otherwise unspecified.
+ * DGV2_EINVAL, nothing launched: a null out / acc / points / colors, B, N or a size < 1, C outside [1, 4], N >= 2^22,
+ * more than 2^31 - 1 blocks.
+ * ------------------------------------------------------------------------- */
+int dgv2_bev_render(float* out, int64_t* acc, const float* points, const float* colors, const float* R, const float* t,
+                    int B, int N, int C, int size, float focal, void* stream);
+int dgv2_bilinear_splat(float* out, int64_t* acc, const float* coords, const float* values, int B, int N, int C, int H,
+                        int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
