@@ -44,6 +44,10 @@ $(BUILD)/sgd.o: HIPFLAGS += -ffp-contract=off
 # two roundings, not a fused multiply-add that float32 restatements of the contract would not make
 $(BUILD)/bev.o: HIPFLAGS += -ffp-contract=off
 
+# latent.hip states Adam's update per operation in float32 (include/dgv2.h "Latent fitting"): m / denom is rounded before
+# it is scaled and subtracted, as torch's addcdiv_ rounds it
+$(BUILD)/latent.o: HIPFLAGS += -ffp-contract=off
+
 $(LIB): $(OBJ)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ)

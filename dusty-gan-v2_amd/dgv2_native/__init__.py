@@ -180,6 +180,7 @@ SIGNATURES = {
     "dgv2_cam_fwd": [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr],
     "dgv2_bev_render": [_c_ptr] * 6 + [_c_int] * 4 + [_c_f32, _c_ptr],
     "dgv2_bilinear_splat": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr],
+    "dgv2_latent_step": [_c_ptr] * 12 + [_c_int] * 4 + [_c_f32] * 7 + [_c_int, _c_ptr],
 }
 
 

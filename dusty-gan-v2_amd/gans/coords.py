@@ -43,6 +43,16 @@ def synthetic_angle_grid(H=64, W0=2048):
     return np.stack([elev, azim], axis=-1).astype(np.float32)
 
 
+def frontal_angle_grid(H=64, W=512):
+    """The rays of the frontal simulated scans (semseg.datasets.SyntheticFrontal; the SqueezeSeg / GTA-LiDAR layout):
+    elevation +2 .. -24.8 degrees over H rings, azimuth +45 .. -45 degrees over W columns, [H,W,2] = (elevation,
+    azimuth).  A trained generator is an implicit field over angles: CoordBridge(angle_array=this) queries it on the
+    simulator's grid instead of the sensor's."""
+    elev = np.deg2rad(np.linspace(2.0, -24.8, H))[:, None].repeat(W, 1)
+    azim = np.deg2rad(np.linspace(45.0, -45.0, W))[None, :].repeat(H, 0)
+    return np.stack([elev, azim], axis=-1).astype(np.float32)
+
+
 class CoordBridge(nn.Module):
     def __init__(self, num_ring, num_points, min_depth, max_depth, angle_file=None, raydrop_const=0,
                  angle_array=None):

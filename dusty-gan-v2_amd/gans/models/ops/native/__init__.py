@@ -14,8 +14,8 @@ and ends in a literal __all__; a module-level switch (a name read from os.enviro
 scripts read and set it as <module>.<FLAG>.  Everything in a submodule's __all__ is also reachable as native.<name>.
 """
 import dgv2_native as N  # noqa: F401  (native.N: the ctypes binding)
-from . import (act_resample, cam, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, loss, modgemm, modlayer,  # noqa: F401
-               modup, optim, render, rng, second_order, segloss, sgd, stem_tail_ada)
+from . import (act_resample, cam, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, latent, loss, modgemm,  # noqa: F401
+               modlayer, modup, optim, render, rng, second_order, segloss, sgd, stem_tail_ada)
 from .act_resample import *  # noqa: F401,F403
 from .fourier import *  # noqa: F401,F403
 from .glin import *  # noqa: F401,F403
@@ -39,3 +39,4 @@ from .fire import *  # noqa: F401,F403
 from .cam import *  # noqa: F401,F403
 from .sgd import *  # noqa: F401,F403
 from .render import *  # noqa: F401,F403
+from .latent import *  # noqa: F401,F403

@@ -1329,6 +1329,41 @@ int dgv2_bev_render(float* out, int64_t* acc, const float* points, const float* 
 int dgv2_bilinear_splat(float* out, int64_t* acc, const float* coords, const float* values, int B, int N, int C, int H,
                         int W, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Latent fitting: what a stage-1 inversion step does after backward(), in one launch (latent.hip; gans/sim2real.py here)
+ * replaces: inversion.py:10-20,81-90 and demo_inversion.py:147-152 -- geocross_loss and autograd through it, the
+ *   LambdaLR schedule (a Python float per step, which keeps the step out of a hipGraph), torch.optim.Adam /
+ *   SphericalOptimizer on the latent and the phase, and the host-side append of the loss: about 50 launches on a few KB.
+ * z, g_z, m_z, v_z [B,N,D] (N = 1 for the latent types "w" and "z"); phase, g_phase, m_p, v_p [B,2], all four NULL = the
+ * phase is not optimised; step int32 [B]; loss_terms [B] (the data terms autograd produced); loss_log [num_steps,B];
+ * geo [B] (output).  All float32 (step: int32) and contiguous.  One block per sample, no atomics, no workspace, no
+ * dependence between samples: a sample's bits depend neither on B nor on its place in the batch, and are the same from
+ * run to run (block sums: strided partial, xor shuffle, wave partials in order).
+ * Per sample b, with k = step[b]; k outside [0, num_steps) leaves everything of that sample untouched (an over-replayed
+ * graph is harmless):
+ *   1. geo[b] = mean over all N^2 ordered pairs (i, j), the diagonal included, of atan2(A, B)^3  (= (2 atan2)^3 / 8),
+ *      A = sqrt(|x_i - x_j|^2 + 1e-9), B = sqrt(|x_i + x_j|^2 + 1e-9), both sums taken over the differences / sums
+ *      themselves (equal styles give exactly 0 + 1e-9; a Gram form would not).  g_z += geo_coef * d geo / d z (analytic).
+ *      geo_coef = 0 skips the term (geo[b] = 0, g_z not written); the reference's "w+" value is 5e-3.
+ *   2. loss_log[k,b] = loss_terms[b] + geo_coef * geo[b]
+ *   3. lr = lr0 * gamma(k): t = k / num_steps, gamma = min(1, (1 - t) / rampdown_ratio),
+ *      gamma = (0.5 - 0.5 cos(pi gamma)) * min(1, t / rampup_ratio), in double.  gamma(0) = 0: the first step moves the
+ *      moments and leaves the parameters bit-unchanged.
+ *   4. torch.optim.Adam's update of z and phase (no weight decay, no amsgrad), bias corrections with k + 1; the scalar
+ *      factors (1 - beta, lr / (1 - beta1^(k+1)), sqrt(1 - beta2^(k+1))) in double from the float arguments, rounded once;
+ *      element-wise in float32:  m += (1 - beta1) (g - m);  v = v beta2 + (1 - beta2) g g;
+ *      p -= step_size * (m / (sqrt(v) / bias2_sqrt + eps))
+ *   5. hypersphere != 0: every row z[b,n,:] is divided by sqrt(mean(row^2) + 1e-9) after the update (phase is not).
+ *   6. step[b] = k + 1
+ * DGV2_EINVAL, nothing launched: a null z / g_z / m_z / v_z / step / loss_terms / loss_log / geo; B, N, D or num_steps
+ * < 1; N * D > 16384 (the sample's z is held in LDS); geo_coef != 0 with N < 2; the four phase pointers neither all
+ * NULL nor all set.  The launch function allocates and synchronises nothing: it may be captured into a hipGraph.
+ * ------------------------------------------------------------------------- */
+int dgv2_latent_step(float* z, float* g_z, float* m_z, float* v_z, float* phase, const float* g_phase, float* m_p,
+                     float* v_p, int* step, const float* loss_terms, float* loss_log, float* geo, int B, int N, int D,
+                     int num_steps, float lr0, float rampup_ratio, float rampdown_ratio, float beta1, float beta2,
+                     float eps, float geo_coef, int hypersphere, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
