@@ -28,7 +28,6 @@ from torch.nn.modules.utils import _pair
 
 from . import base, dusty_v1, ops
 from .ops import native
-from .ops.fourier import _CONST_CACHE
 
 LOW = torch.bfloat16
 
@@ -540,26 +539,15 @@ class SynthesisNetwork(nn.Module):
                 m._cvec_ready = True
 
     def _angle_pyramid(self, angle):
-        """[coarsest ... finest] unshifted angle grids of a batch-shared grid; cached like FourierFeature.encoded (the
-        sensor's grid is a constant; not while a hipGraph is being captured)."""
-        key = (angle._version, tuple(angle.shape))
-        if getattr(self, "_pyr_src", None) is angle and self._pyr_key == key:   # same tensor object, unmodified
-            return self._pyr
-        pyr, a = [angle], angle
-        for layer in self.layers[:0:-1]:
-            a = layer.downsample_angle(a, None, None)
-            pyr.insert(0, a)
-        if _CONST_CACHE and not (angle.is_cuda and torch.cuda.is_current_stream_capturing()):
-            old = getattr(self, "_pyr", None)
-            if (old is not None and len(old) == len(pyr)
-                    and all(a.shape == b.shape and a.dtype == b.dtype and a.device == b.device for a, b in zip(old, pyr))):
-                # refreshed IN PLACE (FourierFeature.encoded explains why): graphs captured on the old pyramid keep
-                # reading these addresses.  Level -1 is the caller's own tensor.
-                for a, b in zip(old[:-1], pyr[:-1]):
-                    a.copy_(b)
-                pyr = old[:-1] + [angle]
-            self._pyr_src, self._pyr_key, self._pyr = angle, key, pyr
-        return pyr
+        """[coarsest ... finest] unshifted angle grids of a batch-shared grid.  The sensor's grid is a constant, so the
+        derived levels are kept under native.ConstCache's rule; the finest level is the caller's own tensor."""
+        def levels():
+            out, a = [], angle
+            for layer in self.layers[:0:-1]:
+                a = layer.downsample_angle(a, None, None)
+                out.insert(0, a)
+            return out
+        return native.ConstCache.on(self, "_cc_pyramid").get((angle,), tuple(angle.shape), levels) + [angle]
 
     def _batched_styles(self, ws):
         """All style affines (EqualLR Linear of every ModConv2d on the fused path) as one batched GEMM; each

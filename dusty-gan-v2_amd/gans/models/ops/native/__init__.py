@@ -14,9 +14,10 @@ and ends in a literal __all__; a module-level switch (a name read from os.enviro
 scripts read and set it as <module>.<FLAG>.  Everything in a submodule's __all__ is also reachable as native.<name>.
 """
 import dgv2_native as N  # noqa: F401  (native.N: the ctypes binding)
-from . import (act_resample, cam, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, latent, loss, modgemm,  # noqa: F401
+from . import (act_resample, cam, constcache, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, latent, loss, modgemm,  # noqa: F401
                modlayer, modup, optim, render, rng, second_order, segloss, sgd, stem_tail_ada)
 from .act_resample import *  # noqa: F401,F403
+from .constcache import *  # noqa: F401,F403
 from .fourier import *  # noqa: F401,F403
 from .glin import *  # noqa: F401,F403
 from .optim import *  # noqa: F401,F403

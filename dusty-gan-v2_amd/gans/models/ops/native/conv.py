@@ -13,6 +13,7 @@ from torch.autograd import Function
 import dgv2_native as N
 from . import act_resample
 from .act_resample import ResampleSpec, _BiasActBackward, _Resample, _dt, _resample_raw, want_param_grad
+from .constcache import versioned
 from .fp8 import _conv_fwd_fp8, _handle, _resample_q8_raw, fp8_dequant
 from .modgemm import _values
 
@@ -185,12 +186,7 @@ def _conv_dgrad_raw(gy, w, g, xshape, wt=None, resid=None, w8t=None):
                       N.ptr(resid), N.stream()):
             return gx
     if wt is None:   # cached on the values tensor (see modgemm._values): first and second pass of R1 share it
-        c = getattr(w, "_dgv2_vals_t", None)
-        if c is not None and c[0] == w._version:
-            wt = c[1]
-        else:
-            wt = w.permute(3, 1, 2, 0).contiguous()
-            w._dgv2_vals_t = (w._version, wt)
+        wt = versioned(w, "_dgv2_vals_t", lambda: w.permute(3, 1, 2, 0).contiguous())
     N.check(gy, wt, resid)
     if (w is not None and _X3_AUTO[0] and gy.dtype == torch.float32 and g.ring3x3 and g.stride == 1
             and W % 32 == 0 and H >= 2 and C % 64 <= 16):

@@ -10,6 +10,7 @@ from torch.autograd import Function
 
 import dgv2_native as N
 from .act_resample import _BiasActBackward, _dt, _sq_tail
+from .constcache import versioned
 
 
 # ---------------------------------------------------------------------------------------
@@ -239,12 +240,7 @@ def _values(w, dtype):
     # (a fresh `weight * gain` per forward; `_version` guards a parameter used directly)
     if w.dtype == dtype and w.is_contiguous():
         return w.detach()
-    c = getattr(w, "_dgv2_vals", None)
-    if c is not None and c[0] == w._version and c[1].dtype == dtype:
-        return c[1]
-    v = w.detach().to(dtype).contiguous()
-    w._dgv2_vals = (w._version, v)
-    return v
+    return versioned(w, "_dgv2_vals", lambda: w.detach().to(dtype).contiguous(), ok=lambda v: v.dtype == dtype)
 
 
 __all__ = ["bmm_nn_sq_call", "bmm_nn_cat_sq_call", "bmm_tn_call", "bmm_tn_cat_call", "mod_gemm", "mod_gemm_act",

@@ -11,6 +11,7 @@ from torch.autograd import Function
 import dgv2_native as N
 from . import act_resample, conv
 from .act_resample import _dt, _resample_raw, _sq_args, _sq_partials, _sq_tail
+from .constcache import ConstCache
 from .modgemm import _bmm_nn_raw, bmm_tn_call
 from .modlayer import _bmm_tn_stream, _mod_act_bwd, _mod_wgrad, pe_wgrad
 
@@ -26,19 +27,9 @@ from .modlayer import _bmm_tn_stream, _mod_act_bwd, _mod_wgrad, pe_wgrad
 _UP_COMMUTE = os.environ.get("DGV2_NO_UP_COMMUTE") is None   # A/B switch for benchmarking
 
 
-def _spec_cache(spec, name):
-    """A per-spec dict (an id()-keyed module dict would hand a dead spec's tables to a new object at its address)."""
-    c = spec.__dict__.get(name)
-    if c is None:
-        c = {}
-        setattr(spec, name, c)
-    return c
-
-
 def _up_tables(spec, hl, wl, device):
     """Two-tap tables (low-res index, weight) per output row / column of an up-2 Resample, zero-padded to two taps."""
-    key = (hl, wl, str(device))
-    _UP_TABLES = _spec_cache(spec, "_dgv2_up_tables")
+    key, _UP_TABLES = (hl, wl, False, str(device), "up_tables"), spec._tab     # (the spec's own table dict, like bands())
     if key not in _UP_TABLES:
         (ih, ch, _, Eh), (iw, cw, _, Ew) = spec.tables(hl, wl, False, device)
         if Eh > 2 or Ew > 2:
@@ -64,8 +55,7 @@ def _up_gram(spec, hl, wl, device):
     """Diagonal / first off-diagonal of the Gram matrices Uh^T Uh, Uw^T Uw of an up-2 Resample's axis factors (fp32
     device vectors ghd, gho [hl], gwd, gwo [wl]; the W axis is a ring: gwo[j] couples j and (j + 1) % wl), or None when
     a Gram matrix is not tridiagonal (then the statistic needs the pass at the up-sampled size)."""
-    key = (hl, wl, str(device))
-    _UP_GRAM = _spec_cache(spec, "_dgv2_up_gram")
+    key, _UP_GRAM = (hl, wl, False, str(device), "up_gram"), spec._tab
     if key not in _UP_GRAM:
         (ih, ch, _, _), (iw, cw, _, _) = spec.tables(hl, wl, False, device)
 
@@ -106,28 +96,15 @@ def up2_lag_sumsq(x, spec):
     return sq[0][:sq[1].value]
 
 
-def pe_frag16(xs, refresh=False):
+def pe_frag16(xs, stale=False):
     """The batch-shared PE [1,H,W,Ks] as the B-fragment image of dgv2_modconv_up_fwd, [H*W/16][Ks/32][4][16][8]: element
     [p][k] at [p/16][k/32][(k%32)/8][p%16][k%8].  The PE is a constant of the run (FourierFeature.encoded caches it), so
-    the image is built once per PE tensor and version and lives ON that tensor (captured graphs read it for as long as
-    the PE exists; a process-wide cache with eviction would free it under them).  Built inside a capture it is not kept.
-    refresh: xs was rewritten in place by a native call (FourierFeature.encoded refreshing its table; no version bump):
-    an existing image is rebuilt IN PLACE, so that graphs which captured its address read the new table."""
-    ent = getattr(xs, "_dgv2_frag16", None)
-    if ent is not None and ent[0] == xs._version and not refresh:
-        return ent[1]
+    the image is built once per PE tensor and version and its ConstCache lives ON that tensor (captured graphs read it for
+    as long as the PE exists; a process-wide cache with eviction would free it under them).
+    stale: xs was rewritten in place by a native call (FourierFeature.encoded refilling its table; no version bump)."""
     P, Ks = xs.shape[1] * xs.shape[2], xs.shape[3]
-    src = xs.reshape(P // 16, 16, Ks // 32, 4, 8).permute(0, 2, 3, 1, 4)
-    if ent is not None and not (xs.is_cuda and torch.cuda.is_current_stream_capturing()):
-        ent[1].copy_(src)
-        xs._dgv2_frag16 = (xs._version, ent[1])
-        return ent[1]
-    if refresh:
-        return None          # nothing to refresh yet
-    img = src.contiguous()
-    if not (xs.is_cuda and torch.cuda.is_current_stream_capturing()):
-        xs._dgv2_frag16 = (xs._version, img)
-    return img
+    return ConstCache.on(xs, "_dgv2_cc_frag16").get(
+        (xs,), None, lambda: xs.reshape(P // 16, 16, Ks // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous(), stale)
 
 
 # output widths the commuted form runs at: 32 (level 4), 64 / 128 (levels 3 / 2, round 4: 32-channel slabs of the same
