@@ -48,6 +48,10 @@ $(BUILD)/bev.o: HIPFLAGS += -ffp-contract=off
 # it is scaled and subtracted, as torch's addcdiv_ rounds it
 $(BUILD)/latent.o: HIPFLAGS += -ffp-contract=off
 
+# syncbn.hip promises the same bits from its 16-byte and element-wise paths and from every split of a batch over ranks:
+# no instantiation may fuse a float64 multiply into an add that another leaves alone
+$(BUILD)/syncbn.o: HIPFLAGS += -ffp-contract=off
+
 $(LIB): $(OBJ)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ)

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGV2_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libdgv2.so")
 
 F32, BF16 = 0, 1
-F16 = 3   # the dgv2_seg_loss_* entries, dgv2_fire_fwd and dgv2_cam_fwd only
+F16 = 3   # the dgv2_seg_loss_* entries, dgv2_fire_fwd, dgv2_cam_fwd and the dgv2_bn_* entries only
 ABI_VERSION = 60
 
 _c_int, _c_i64, _c_f32, _c_ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -181,6 +181,11 @@ SIGNATURES = {
     "dgv2_bev_render": [_c_ptr] * 6 + [_c_int] * 4 + [_c_f32, _c_ptr],
     "dgv2_bilinear_splat": [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr],
     "dgv2_latent_step": [_c_ptr] * 12 + [_c_int] * 4 + [_c_f32] * 7 + [_c_int, _c_ptr],
+    # synchronised batch norm of the segmentation models (csrc/syncbn.hip; replaces torch.nn.SyncBatchNorm)
+    "dgv2_bn_partials": [_c_ptr, _c_ptr] + [_c_int] * 5 + [_c_ptr],
+    "dgv2_bn_apply": [_c_ptr] * 10 + [_c_int] * 5 + [_c_f32, _c_f32, _c_int, _c_ptr],
+    "dgv2_bn_bwd_partials": [_c_ptr] * 5 + [_c_int] * 5 + [_c_ptr],
+    "dgv2_bn_bwd_apply": [_c_ptr] * 9 + [_c_int] * 7 + [_c_ptr],
 }
 
 

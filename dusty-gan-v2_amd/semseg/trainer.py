@@ -1,21 +1,28 @@
-"""Training of the range-image segmentation models on one GPU (reference: train_semseg.py:136-212 the builders,
-243-362 the loop).  The trunk's training forward and backward are the library composition under autograd (DESIGN.md
+"""Training of the range-image segmentation models, one process per GPU (reference: train_semseg.py:136-212 the
+builders, 243-362 the loop).  The trunk's training forward and backward are the library composition under autograd (DESIGN.md
 section 31); the loss is the native masked focal loss (section 29) and the tail of the step -- unscale, global-norm
 clip, SGD with momentum, loss-scale update -- runs on csrc/sgd.hip (section 34), without a host synchronisation.
 
-Not here: DistributedDataParallel / SyncBatchNorm (the reference wraps the model in both), tensorboard images.
+Several ranks (reference: train_semseg.py:172-174, 375-382): every BatchNorm2d becomes a semseg.models.SyncBatchNorm2d
+(csrc/syncbn.hip, section 39) and the gradients are averaged over the ranks on one flat buffer
+(gans.parallel.FlatGradSync) between the backward and the tail.  There is no DistributedDataParallel wrapper: the state
+dict has no "module." prefix.
+
+Not here: tensorboard images.
 """
 import warnings
 
 import torch
+import torch.distributed as dist
 import torch.nn.functional as F
 from torch import optim
 
+from gans import parallel
 from gans.models.ops.native.sgd import fused_clip_sgd_step
 
 from .config import to_plain
 from .metrics import Evaluator
-from .models import MaskedSegLoss, SqueezeSegV1, SqueezeSegV2
+from .models import MaskedSegLoss, SqueezeSegV1, SqueezeSegV2, convert_sync_batchnorm
 
 INIT_SCALE = 65536.0   # torch.amp.GradScaler's defaults
 GROWTH, BACKOFF, GROWTH_INTERVAL = 2.0, 0.5, 2000
@@ -68,15 +75,28 @@ class Trainer:
     fused_optimizer=True: the step's tail is native.fused_clip_sgd_step.  False: torch's clip_grad_norm_ + SGD.step,
     with torch.amp.GradScaler under AMP -- the yardstick of section 34 and the fallback.  Both keep torch's optimizer
     state layout.  self.scale: float32 [2] (loss scale, growth tracker) on the device, None without AMP.
-    self.conf_train: int64 [C+1,C+1] confusion counts of the training predictions since the last reset_conf()."""
+    self.conf_train: int64 [C+1,C+1] confusion counts of THIS rank's training predictions since the last reset_conf();
+    conf_total() sums them over the ranks.
 
-    def __init__(self, cfg, device, fused_optimizer=True, pretrained_weights=True):
+    Under a process group of several ranks (gans.parallel.is_dist()), or with sync_bn=True, the model's batch norms are
+    the native synchronised ones; under a process group the parameters and buffers start as rank 0's and every step
+    averages the gradients over the ranks before its tail, so a float16 overflow on one rank is non-finite on all of
+    them and every rank skips and rescales alike.  One rank and sync_bn unset: nothing of this runs."""
+
+    def __init__(self, cfg, device, fused_optimizer=True, pretrained_weights=True, sync_bn=None):
         self.cfg = cfg
         self.device = torch.device(device)
         self.fused_optimizer = bool(fused_optimizer)
         self.use_amp = bool(cfg.use_amp)
         self.num_classes = int(cfg.dataset.num_classes)
         self.model = build_model(cfg, pretrained_weights=pretrained_weights).to(self.device).train()
+        self.distributed = parallel.is_dist()
+        self.world_size = parallel.world_size()
+        self.sync_bn = bool(sync_bn) or self.distributed
+        if self.sync_bn:
+            convert_sync_batchnorm(self.model)
+        parallel.broadcast_module(self.model)
+        self.grad_sync = parallel.FlatGradSync(self.model) if self.distributed else None
         self.criterion = build_criterion(cfg).to(self.device)
         tr = cfg.training
         self.optimizer = optim.SGD(list(self.model.parameters()), lr=tr.lr, momentum=tr.lr_momentum,
@@ -109,6 +129,25 @@ class Trainer:
     def reset_conf(self):
         self.conf_train.zero_()
 
+    def conf_total(self):
+        """conf_train summed over the ranks (a collective: every rank calls it at the same step); one rank: conf_train."""
+        if not self.distributed:
+            return self.conf_train
+        total = self.conf_train.clone()
+        dist.all_reduce(total, op=dist.ReduceOp.SUM)
+        return total
+
+    def _backward(self, loss):
+        """Fresh gradients of `loss`; under a process group their average over the ranks, in the flat buffer."""
+        if self.grad_sync is None:
+            self.optimizer.zero_grad(set_to_none=True)
+            loss.backward()
+            return
+        self.grad_sync.begin(direct=False)
+        loss.backward()
+        self.grad_sync.collect()
+        self.grad_sync.all_reduce()
+
     def step(self, item):
         """One optimisation step on a batch {"xyz", "depth", "label", "mask"[, "reflectance"]} (any device).
         -> {"loss", "grad_norm", "pred"}: device tensors (the loss times cls_loss_coef, the unscaled total gradient
@@ -131,9 +170,8 @@ class Trainer:
             loss, pred = self.criterion(logit, label, mask, conf=self.conf_train)
         loss = loss * self.loss_coef
 
-        self.optimizer.zero_grad(set_to_none=True)
         if self.fused_optimizer:
-            (loss * self.scale[0] if self.scale is not None else loss).backward()
+            self._backward(loss * self.scale[0] if self.scale is not None else loss)
             sc = fused_clip_sgd_step(self.optimizer, self.max_grad_norm, scale_state=self.scale, growth=GROWTH,
                                      backoff=BACKOFF, growth_interval=GROWTH_INTERVAL)
             grad_norm = sc[0].clone()
@@ -151,11 +189,11 @@ class Trainer:
         """The reference's lines 279-283 on torch's own kernels."""
         params = list(self.model.parameters())
         if self.grad_scaler is None:
-            loss.backward()
+            self._backward(loss)
             grad_norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
             self.optimizer.step()
             return grad_norm.detach()
-        self.grad_scaler.scale(loss).backward()
+        self._backward(self.grad_scaler.scale(loss))
         self.grad_scaler.unscale_(self.optimizer)
         grad_norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
         self.grad_scaler.step(self.optimizer)

@@ -29,7 +29,7 @@ extern "C" {
 #define DGV2_F32 0
 #define DGV2_BF16 1
 #define DGV2_FP8 2 /* OCP e4m3fn bytes; only where an entry says so (the *_fp8 / *_q8 entries) */
-#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits; dgv2_fire_fwd; dgv2_cam_fwd) */
+#define DGV2_F16 3 /* IEEE half; only where an entry says so (the dgv2_seg_loss_* entries: AMP's fp16 logits; dgv2_fire_fwd; dgv2_cam_fwd; the dgv2_bn_* entries) */
 #define DGV2_EINVAL (-1)
 #define DGV2_ENOTSUP (-3) /* valid request that this build's kernels do not cover: use the documented fallback */
 
@@ -1363,6 +1363,57 @@ int dgv2_latent_step(float* z, float* g_z, float* m_z, float* v_z, float* phase,
                      float* v_p, int* step, const float* loss_terms, float* loss_log, float* geo, int B, int N, int D,
                      int num_steps, float lr0, float rampup_ratio, float rampdown_ratio, float beta1, float beta2,
                      float eps, float geo_coef, int hypersphere, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Synchronised batch norm of the segmentation models, training mode (syncbn.hip; semseg/models/syncbn.py here)
+ * replaces: torch.nn.SyncBatchNorm as train_semseg.py:172-174 puts it over every BatchNorm2d of semseg/models/common.py
+ *   (batch_norm_stats, an all_gather of means / inverse deviations / counts, batch_norm_gather_stats_with_counts,
+ *   batch_norm_elemt; batch_norm_backward_reduce, an all_reduce, batch_norm_backward_elemt), whose fp32 merge of the
+ *   ranks' statistics depends on how the batch is split over the ranks.
+ * x, y, dy, dx [B,C,H,W] are contiguous NCHW of one `dtype` (DGV2_F32, DGV2_BF16 or DGV2_F16).  weight, bias, the
+ * running buffers and the saved statistics are float32 [C]; num_batches_tracked is ONE int64.  part is float64
+ * [B,C,2] where an entry writes it and [Btot,C,2] where an entry reads it: the blocks of all ranks, rank-major, then
+ * the sample index (the caller gathers them; one rank: the array as written).  All sums and all arithmetic below are
+ * float64; a result is rounded once to float32 and, for a 16-bit dtype, once more to that dtype.
+ *   dgv2_bn_partials      part[b][c] = (sum x, sum x^2) over the plane x[b][c]
+ *   dgv2_bn_apply         (S, Q) = part[0][c] + part[1][c] + ... + part[Btot-1][c], in index order;  n = Btot H W
+ *                         mean = S / n;  var = max(Q / n - mean^2, 0);  invstd = 1 / sqrt(var + eps)
+ *                         y = (x - mean) (invstd weight[c]) + bias[c]            (weight / bias NULL: 1 / 0)
+ *                         save_mean[c] = mean, save_invstd[c] = invstd
+ *                         running_mean[c] = (1 - f) running_mean[c] + f mean
+ *                         running_var[c]  = (1 - f) running_var[c]  + f var n / (n - 1)
+ *                         f = momentum, and num_batches_tracked += 1 (NULL: not counted);  momentum < 0 is torch's
+ *                         momentum=None, the cumulative average: f = 1 / num_batches_tracked, which the CALLER has
+ *                         already incremented for this batch (every channel's block reads the word, so none writes it).
+ *                         running_mean and running_var both NULL: no running statistics.
+ *   dgv2_bn_bwd_partials  part[b][c] = (sum dy, sum dy xhat),  xhat = (x - mean[c]) invstd[c] from the SAVED float32 values
+ *   dgv2_bn_bwd_apply     (S, Q) as above over the gathered backward partials;  m1 = S / n, m2 = Q / n
+ *                         dx = (invstd[c] weight[c]) ((dy - m1) - xhat m2)
+ *                         dbias[c] = part[b_off][c][0] + ... + part[b_off+B-1][c][0], dweight[c] the same over [1]: the
+ *                         LOCAL samples only, torch.nn.SyncBatchNorm's semantics (the gradient reduction averages them
+ *                         over the ranks afterwards); either may be NULL.
+ * One block per plane.  A plane's sums are added in an order that its size H W and the dtype fix -- not B, not the
+ * grid, not the plane's address (16-byte loads where a plane is 16-byte aligned, the same groups element by element
+ * where it is not; syncbn.hip spells the order out) -- and the fold runs in index order on every rank, so the
+ * statistics, y and dx are the same bits however Btot samples are split over ranks, and from run to run.  No atomics,
+ * no workspace (the partials are outputs: there is no _scratch sibling).  In dgv2_bn_apply the block of sample 0 of a
+ * channel writes that channel's statistics and running buffers, and block 0 counts the batch.
+ * DGV2_EINVAL, nothing launched: a null required pointer (everything but weight, bias, the running buffers,
+ * num_batches_tracked, dweight, dbias), one running buffer without the other, momentum < 0 with running buffers and
+ * no num_batches_tracked, B, C, H or W < 1, B C, Btot C or H W above 2^31 - 1, Btot < B, b_off outside
+ * [0, Btot - B], another dtype, a negative or NaN eps, a NaN momentum, and Btot H W == 1 (torch: "Expected more than 1
+ * value per channel when training").
+ * ------------------------------------------------------------------------- */
+int dgv2_bn_partials(double* part, const void* x, int B, int C, int H, int W, int dtype, void* stream);
+int dgv2_bn_apply(void* y, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                  int64_t* num_batches_tracked, const void* x, const double* part, const float* weight,
+                  const float* bias, int B, int Btot, int C, int H, int W, float eps, float momentum, int dtype,
+                  void* stream);
+int dgv2_bn_bwd_partials(double* part, const void* dy, const void* x, const float* mean, const float* invstd, int B,
+                         int C, int H, int W, int dtype, void* stream);
+int dgv2_bn_bwd_apply(void* dx, float* dweight, float* dbias, const void* dy, const void* x, const double* part,
+                      const float* mean, const float* invstd, const float* weight, int B, int Btot, int b_off, int C,
+                      int H, int W, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,10 @@
     float32 and under AMP (float16 autocast), after --warmup steps: mean and smallest time per phase over --steps.
 
     python scripts/mb_semseg_step.py [--rounds 3] [--calls 50] [--batch 40] [--steps 20] [--warmup 20] [--skip_step]
+                                     [--skip_tail] [--sync_bn]
+
+--sync_bn measures (b) with the model's batch norms swapped for the native synchronised ones (section 39) beside the
+library's, the two alternating.
 
 Prints one JSON line per measurement."""
 import argparse
@@ -109,10 +113,10 @@ def measure_tail(cfg, amp, rounds, calls):
                           "kernels": sorted(set(names))[:12]}), flush=True)
 
 
-def measure_step(cfg, amp, batch, steps, warmup, fused):
+def measure_step(cfg, amp, batch, steps, warmup, fused, sync_bn=False):
     cfg.use_amp = amp
     torch.manual_seed(0)
-    tr = Trainer(cfg, DEV, fused_optimizer=fused, pretrained_weights=False)
+    tr = Trainer(cfg, DEV, fused_optimizer=fused, pretrained_weights=False, sync_bn=sync_bn)
     data = SyntheticFrontal(batch, tuple(cfg.dataset.shape), cfg.dataset.num_classes, seed=0)
     item = next(iter(torch.utils.data.DataLoader(data, batch_size=batch)))
     item = tr._to_device(item)
@@ -149,7 +153,7 @@ def measure_step(cfg, amp, batch, steps, warmup, fused):
         if it >= warmup:
             for k, a, b in zip(phases, ev[:-1], ev[1:]):
                 times[k].append(a.elapsed_time(b))
-    row = {"measure": "step", "amp": amp, "fused_optimizer": fused, "batch": batch, "shape": list(cfg.dataset.shape),
+    row = {"measure": "step", "amp": amp, "fused_optimizer": fused, "sync_bn": sync_bn, "batch": batch, "shape": list(cfg.dataset.shape),
            "loss_scale": tr.loss_scale(), "loss": float(loss)}
     for k in phases:
         row[k + "_ms_mean"] = round(sum(times[k]) / len(times[k]), 3)
@@ -166,11 +170,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--skip_step", action="store_true")
+    ap.add_argument("--skip_tail", action="store_true")
+    ap.add_argument("--sync_bn", action="store_true")
     args = ap.parse_args()
     cfg = default_config()
-    for amp in (False, True):
-        measure_tail(cfg, amp, args.rounds, args.calls)
-    if not args.skip_step:
+    if not args.skip_tail:
+        for amp in (False, True):
+            measure_tail(cfg, amp, args.rounds, args.calls)
+    if args.sync_bn:
+        for amp in (False, True):
+            for sync_bn in (False, True, False, True):
+                measure_step(default_config(), amp, args.batch, args.steps, args.warmup, True, sync_bn=sync_bn)
+    elif not args.skip_step:
         for amp in (False, True):
             for fused in (True, False):
                 measure_step(default_config(), amp, args.batch, args.steps, args.warmup, fused)
