@@ -186,6 +186,8 @@ SIGNATURES = {
     "dgv2_bn_apply": [_c_ptr] * 10 + [_c_int] * 5 + [_c_f32, _c_f32, _c_int, _c_ptr],
     "dgv2_bn_bwd_partials": [_c_ptr] * 5 + [_c_int] * 5 + [_c_ptr],
     "dgv2_bn_bwd_apply": [_c_ptr] * 9 + [_c_int] * 7 + [_c_ptr],
+    # one PointNet trunk of the FPD / KPD feature extractor (csrc/pointnet.hip; gans/metrics/pointnet.py)
+    "dgv2_pointnet_trunk": [_c_ptr] * 9 + [_c_int] * 3 + [_c_ptr],
 }
 
 

@@ -3,15 +3,35 @@
 Reference: gans/metrics/pointnet.py:8-94 (the classifier of microsoft/SpareNet's Frechet point-cloud distance).  The
 parameter and buffer names are the compatibility contract -- `cls_model_39.pth` must load with strict=True -- so the
 module tree (STN3d / PointNetfeat / PointNet1, Conv1d / Linear / BatchNorm1d leaves) is the reference's; what differs
-is how it is evaluated: inference only, the batch norms folded into the preceding affine map once per call, the
-per-point layers as plain library GEMMs over [points, channels] rows, and the clouds walked in chunks so that the
-1024-channel activation of a 64 x 512 scan (134 MB per cloud in fp32) never exceeds ~2 GB.
+is how it is evaluated: inference only, the batch norms folded into the preceding affine map once per call.  On the
+device each trunk (the per-point 3 -> 64 -> 128 -> 1024 layers and the max over the points) is one call of
+gans.models.ops.native.pointnet for the whole batch, which keeps no per-point activation in memory (DESIGN.md section
+40).  On the CPU, with POINTNET_NATIVE off, or above the kernel's size cap, the per-point layers are plain library GEMMs
+over [points, channels] rows and the clouds are walked in chunks so that the 1024-channel activation of a 64 x 512 scan
+(134 MB per cloud in fp32) never exceeds ~2 GB.
 """
 import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from gans.models.ops.native import pointnet as _pointnet
+
+# False forces the library-GEMM composition and the chunk loop on the device too (tests, A/B timing); read at every
+# call.  DESIGN.md section 40 has the measurement behind the default.
+POINTNET_NATIVE = True
+
+
+def uses_native(pts):
+    """Whether the trunks of a float32 [B,N,3] batch go through dgv2_pointnet_trunk."""
+    return bool(POINTNET_NATIVE and pts.is_cuda and pts.dtype == torch.float32
+                and _pointnet.pointnet_supported(pts.size(0), pts.size(1)))
+
+
+def _trunk(pts, trans, layers, relu_last):
+    return _pointnet.pointnet_trunk(pts.contiguous(), trans, *[tuple(t.contiguous() for t in _fold(*pair)) for pair in layers],
+                                    relu_last)
 
 
 def _fold(lin, bn):
@@ -49,9 +69,12 @@ class STN3d(nn.Module):
     def forward(self, pts):
         """pts [B, N, 3] (points as rows) -> [B, 3, 3]."""
         _no_training(self)
-        x = F.relu(F.linear(pts, *_fold(self.conv1, self.bn1)))
-        x = F.relu(F.linear(x, *_fold(self.conv2, self.bn2)))
-        x = F.relu(F.linear(x, *_fold(self.conv3, self.bn3))).amax(dim=1)   # [B, 1024]
+        if uses_native(pts):
+            x = _trunk(pts, None, ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)), True)
+        else:
+            x = F.relu(F.linear(pts, *_fold(self.conv1, self.bn1)))
+            x = F.relu(F.linear(x, *_fold(self.conv2, self.bn2)))
+            x = F.relu(F.linear(x, *_fold(self.conv3, self.bn3))).amax(dim=1)   # [B, 1024]
         x = F.relu(F.linear(x, *_fold(self.fc1, self.bn4)))
         x = F.relu(F.linear(x, *_fold(self.fc2, self.bn5)))
         x = F.linear(x, *_plain(self.fc3)).view(-1, 3, 3)
@@ -76,6 +99,9 @@ class PointNetfeat(nn.Module):
         if not self.global_feat:
             raise NotImplementedError("only the global feature (the one FPD / KPD use) is built")
         trans = self.stn(pts)
+        if uses_native(pts):   # pts @ trans happens inside the launch
+            layers = ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3))
+            return _trunk(pts, trans.contiguous(), layers, False), trans
         x = torch.bmm(pts, trans)
         x = F.relu(F.linear(x, *_fold(self.conv1, self.bn1)))
         x = F.relu(F.linear(x, *_fold(self.conv2, self.bn2)))
@@ -102,8 +128,11 @@ class PointNet1(nn.Module):
         if x.dim() != 3 or x.size(1) != 3:
             raise RuntimeError(f"expected (B,3,N), but got {tuple(x.shape)}")
         pts = x.transpose(1, 2).float()
-        chunk = max(1, int(self.ACT_BYTES // (1024 * 4 * pts.size(1))))
-        x1 = torch.cat([self.feat(pts[i:i + chunk].contiguous())[0] for i in range(0, pts.size(0), chunk)])
+        if uses_native(pts):   # no per-point activation exists: the whole batch in one call per trunk
+            x1 = self.feat(pts.contiguous())[0]
+        else:
+            chunk = max(1, int(self.ACT_BYTES // (1024 * 4 * pts.size(1))))
+            x1 = torch.cat([self.feat(pts[i:i + chunk].contiguous())[0] for i in range(0, pts.size(0), chunk)])
         x2 = F.relu(F.linear(x1, *_fold(self.fc1, self.bn1)))
         x3 = F.relu(F.linear(x2, *_fold(self.fc2, self.bn2)))
         x4 = F.linear(x3, *_plain(self.fc3))

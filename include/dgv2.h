@@ -1415,6 +1415,47 @@ int dgv2_bn_bwd_apply(void* dx, float* dweight, float* dbias, const void* dy, co
                       const float* mean, const float* invstd, const float* weight, int B, int Btot, int b_off, int C,
                       int H, int W, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * PointNet trunk of the FPD / KPD feature extractor (pointnet.hip; gans/metrics/pointnet.py here)
+ * replaces: gans/metrics/pointnet.py:22-26 (the spatial transformer's conv1-3 / bn1-3, ReLUs and torch.max over the
+ *   points) and :46-55 (the bmm with the transform, the feature trunk's conv1-3 / bn1-3 and its max): per trunk three
+ *   GEMMs, their activations and a reduction over a [B,N,1024] tensor -- with a launch that keeps no per-point value
+ *   in memory.
+ * pts [B,N,3] (points as rows), trans [B,3,3] or NULL, feat [B,1024]; w1 [64,3], b1 [64], w2 [128,64], b2 [128],
+ * w3 [1024,128], b3 [1024] are the three affine maps with the evaluation-mode batch norms already folded in.  All
+ * float32 and contiguous; w2 and w3 16-byte aligned (they are read with 16-byte loads).  The widths 3 / 64 / 128 / 1024
+ * are the contract.  Per cloud b and point p, in float32:
+ *   q[j]   = fmaf(z, T[2][j], fmaf(y, T[1][j], x * T[0][j])),  (x, y, z) = pts[b][p], T = trans[b]      (the bmm);
+ *            trans == NULL: q = (x, y, z)
+ *   h1[c]  = relu(fmaf(w1[c][2], q[2], fmaf(w1[c][1], q[1], w1[c][0] * q[0])) + b1[c])
+ *   h2[c]  = relu(S_64(w2[c], h1) + b2[c])
+ *   h3[c]  = S_128(w3[c], h2) + b3[c],  through a ReLU when relu_last == 1 (the transformer's trunk: 1, the feature
+ *            trunk: 0)
+ *   feat[b][c] = max over p of h3[c]
+ * S_K(w, h) is ONE fmaf chain from 0 over all K products (the exact v_mfma_f32_32x32x2_f32; no bf16 split), in the
+ * fixed order k = 0, 4, 1, 5, 2, 6, 3, 7, then the same pattern from 8, 16, ...  The order does not depend on where a
+ * point sits, and a maximum does not depend on the order of its operands, so a cloud's features are the same bits
+ * alone or in a batch, under any permutation or repetition of its points, under any split of N over blocks and from
+ * run to run.  A block owns DGV2_POINTNET_TILE points of one cloud and keeps them in registers and LDS through all
+ * three layers; in a ragged tile the lanes beyond N repeat the cloud's last point, so nothing that is not an image of
+ * a point of the cloud enters the maximum.  N > DGV2_POINTNET_TILE: the blocks of a cloud combine their maxima in
+ * feat with integer atomic max / min on the floats' bits after a launch that fills feat with -inf (two launches;
+ * otherwise one).  No workspace: there is no _scratch sibling.  Nothing allocates or synchronises; the launches may
+ * be captured into a hipGraph.
+ * Non-finite coordinates or parameters are outside the contract (a NaN is dropped by the maximum where torch
+ * propagates it); nothing is read back to check.
+ * Range: B, N >= 1, 64-bit offsets; B * ceil(N / DGV2_POINTNET_TILE) <= DGV2_POINTNET_MAX_TILES, above which the entry
+ * returns DGV2_ENOTSUP (fallback: the library-GEMM composition of gans/metrics/pointnet.py).  DGV2_EINVAL: a null
+ * pointer other than trans, B or N < 1, relu_last not 0 / 1, a misaligned w2 / w3.  On every refusal nothing is
+ * launched and feat is untouched.
+ * ------------------------------------------------------------------------- */
+#define DGV2_POINTNET_TILE 128
+#define DGV2_POINTNET_FEATURES 1024
+#define DGV2_POINTNET_MAX_TILES (1 << 28)
+int dgv2_pointnet_trunk(float* feat, const float* pts, const float* trans, const float* w1, const float* b1,
+                        const float* w2, const float* b2, const float* w3, const float* b3, int B, int N,
+                        int relu_last, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
