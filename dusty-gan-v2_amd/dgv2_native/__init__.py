@@ -188,6 +188,9 @@ SIGNATURES = {
     "dgv2_bn_bwd_apply": [_c_ptr] * 9 + [_c_int] * 7 + [_c_ptr],
     # one PointNet trunk of the FPD / KPD feature extractor (csrc/pointnet.hip; gans/metrics/pointnet.py)
     "dgv2_pointnet_trunk": [_c_ptr] * 9 + [_c_int] * 3 + [_c_ptr],
+    # beam upsampling (csrc/upsample.hip; gans/upsampling.py): hold-out masks + baselines, and the depth scores
+    "dgv2_beam_split": [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr],
+    "dgv2_depth_score": [_c_ptr] * 4 + [_c_int, _c_i64, _c_ptr],
 }
 
 

@@ -15,7 +15,7 @@ scripts read and set it as <module>.<FLAG>.  Everything in a submodule's __all__
 """
 import dgv2_native as N  # noqa: F401  (native.N: the ctypes binding)
 from . import (act_resample, cam, constcache, conv, crf, fire, fourier, fp8, frame, glin, inversion, kitti, knn, latent, loss, modgemm,  # noqa: F401
-               modlayer, modup, optim, pointnet, render, rng, second_order, segloss, sgd, stem_tail_ada, syncbn)
+               modlayer, modup, optim, pointnet, render, rng, second_order, segloss, sgd, stem_tail_ada, syncbn, upsample)
 from .act_resample import *  # noqa: F401,F403
 from .constcache import *  # noqa: F401,F403
 from .fourier import *  # noqa: F401,F403
@@ -43,3 +43,4 @@ from .render import *  # noqa: F401,F403
 from .latent import *  # noqa: F401,F403
 from .syncbn import *  # noqa: F401,F403
 from .pointnet import *  # noqa: F401,F403
+from .upsample import *  # noqa: F401,F403

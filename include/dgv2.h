@@ -1456,6 +1456,57 @@ int dgv2_pointnet_trunk(float* feat, const float* pts, const float* trans, const
                         const float* w2, const float* b2, const float* w3, const float* b3, int B, int N,
                         int relu_last, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Beam upsampling: holding out beams of a scan, the interpolation baselines and the depth scores of the held-out
+ * pixels (upsample.hip; gans/upsampling.py here)
+ * replaces: gans/metrics/depth.py:4-45 -- compute_depth_error and compute_depth_accuracy (about 25 tensor-op launches
+ *   and a dozen [B,1,H,W] temporaries per call, summed in float32 in the order the library picks) -- with one launch
+ *   of fixed-order float64 sums; the reference has no code that holds beams out or interpolates them (the paper's
+ *   upsampling table is described, not shipped), so dgv2_beam_split replaces nothing there.
+ *
+ * dgv2_beam_split, one launch: depth, valid [B,1,H,W] float32, contiguous; valid == NULL is 1 everywhere, any other
+ * non-zero value of valid counts as valid.  Row h is observed when h % factor == offset.
+ *   obs  = 1 where the pixel is observed and valid, else 0                              (the fitting mask)
+ *   held = 1 where the pixel is valid and its row is not observed, else 0               (the scoring mask)
+ *   recon, recon_mask: the baseline reconstruction from the observed rows only.  mode 0: nothing is reconstructed and
+ *   both pointers may be NULL; mode 1: nearest; mode 2: linear.  For row h, lo is the nearest observed row with index
+ *   <= h and hi the nearest with index >= h (before the first / after the last observed row only one exists; on an
+ *   observed row lo = hi = h).  A neighbour is valid where it exists and valid says so at (row, w); d_lo, d_hi are the
+ *   depths there.
+ *     linear   both valid: t = (float)(h - lo) / (float)factor;  recon = d_lo + t * (d_hi - d_lo)  -- a float32
+ *              division, subtraction, multiplication and addition, each rounded; lo = hi: recon = d_lo
+ *              one valid: that one's depth;  none: recon = 0, recon_mask = 0
+ *     nearest  the neighbour with the smaller row distance, a tie to lo; if it is not valid the other one if that is;
+ *              else recon = 0, recon_mask = 0
+ *   recon_mask = 1 wherever a value was taken.  Observed rows are therefore copied, and an observed invalid pixel is
+ *   reconstructed from nothing and stays invalid; the pixel's own validity on a row that is not observed plays no part
+ *   in recon.  Depths are read only where valid says so or as operands that are then discarded: non-finite depths at
+ *   valid pixels are outside the contract.
+ * Range: 1 <= factor <= H, 0 <= offset < factor, B, H, W >= 1 (H need not be a multiple of factor).  DGV2_EINVAL,
+ * nothing launched: outside that range, a mode other than 0 .. 2, a null obs / held / depth, a null recon / recon_mask
+ * in mode 1 or 2, more than 2^31 - 1 blocks.
+ *
+ * dgv2_depth_score, one launch, no workspace: ref, gen, mask [B,n] float32, contiguous; mask == NULL is 1 everywhere;
+ * mask is a weight, as in the reference.  Per pixel, in float32, every operation rounded on its own:
+ *   r = ref + 1e-8f;  g = gen + 1e-8f;  d = r - g
+ *   e0 = |d| / r;  e1 = (d * d) / r;  e2 = d * d;  e3 = (logf(r) - logf(g))^2
+ *   delta = max(ref / gen, gen / ref) on the raw values;  a_i = (delta < 1.25^i), i = 1, 2, 3 (1.25, 1.5625, 1.953125:
+ *   exact in float32; a NaN delta compares false)
+ *   sums[b] = { S m e0, S m e1, S m e2, S m e3, S m a1, S m a2, S m a3, S m }: each product m * term is float32, the
+ *   sums S over the n pixels of image b are float64.
+ * A pixel with m == 0 is skipped: the reference multiplies and gives NaN there when the term is not finite.
+ * One block per image.  The order of an image's sums is fixed by n alone (upsample.hip spells it out): no floating-point
+ * atomics, 16-byte loads where the image's three addresses are 16-byte aligned and the same groups element by element
+ * where they are not, so an image's eight sums are the same bits from run to run, alone or in a batch, at any place in
+ * the batch and at any address.  The ratios and square roots of the seven summaries are the caller's.
+ * DGV2_EINVAL, nothing launched: a null sums / ref / gen, B < 1, n < 1 or n >= 2^31.
+ * Neither entry has a workspace (no _scratch sibling), allocates or synchronises: both may be captured into a hipGraph.
+ * ------------------------------------------------------------------------- */
+int dgv2_beam_split(float* recon, float* recon_mask, float* obs, float* held, const float* depth, const float* valid,
+                    int B, int H, int W, int factor, int offset, int mode, void* stream);
+int dgv2_depth_score(double* sums, const float* ref, const float* gen, const float* mask, int B, int64_t n,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
